@@ -9,7 +9,15 @@ of Swin-S 224x224, bf16 autocast, batch 128 per GPU, synthetic data (BASELINE.js
 One process per GPU; RCCL gradient all-reduce (vtx.ddp) overlapped with backward; weak scaling (per-GPU batch
 fixed).  ``python bench.py --gpus N`` with N > 1 and no WORLD_SIZE in the environment launches the N ranks itself
 (re-exec through torch.distributed.run on 127.0.0.1, like the reference's ``dist.launch(main, conf.n_gpu, ...)``,
-train.py:389-396).  Rank 0 prints ONE JSON line.  `roofline` = the HIP kernel with the largest share of the step
+train.py:389-396).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`; `roofline`,
+`measured_peaks`, `cpu_baseline` and `secondary` are null).  ``--full`` adds everything else the line can carry, each
+measured outside the timed region: the event-sampled per-kernel table and `roofline`, the measured MFMA / HBM peaks,
+the CPU baseline and, for the Swin-S headline, the `secondary` workloads.  ``--dump-outputs DIR`` writes what the last
+timed step computed -- its loss and a fixed, seeded sample of the updated parameters -- as float32 .npy files.
+
+With ``--full``: `roofline` = the HIP kernel with the largest share of the step
 (every launch class is bracketed with HIP events on its launch stream in --event-steps steps that run right BEHIND the
 timed region -- same process, same data; they run single-stream so that durations are attributable; the K timed steps
 carry no brackets) + the per-kernel table;
@@ -142,7 +150,8 @@ def _cpu_baseline_dino(batch, steps, cores):
 
 
 def host_cpu():
-    """(physical cores, model name) of this box's host CPU."""
+    """(physical cores this process may use, model name) of this box's host CPU: the host's physical cores, capped by the
+    process's CPU affinity and by OMP_NUM_THREADS when that is set (more threads than CPUs only oversubscribe)."""
     model = "unknown"
     try:
         for line in open("/proc/cpuinfo"):
@@ -156,7 +165,13 @@ def host_cpu():
         cores = psutil.cpu_count(logical=False) or os.cpu_count()
     except Exception:
         cores = os.cpu_count()
-    return int(cores or 1), model
+    cores = int(cores or 1)
+    if hasattr(os, "sched_getaffinity"):
+        cores = min(cores, len(os.sched_getaffinity(0)))
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        cores = min(cores, int(omp))
+    return cores, model
 
 
 def cpu_baseline(name, batch, steps):
@@ -358,9 +373,25 @@ def default_batch(name):
     return 256 if name == "vit_s16" else (64 if name == "dino" else 128)
 
 
-def run_workload(model_name, batch, steps, warmup, args, dev, rank, world):
+DUMP_PARAM_SAMPLE = 1 << 23        # parameters of the --dump-outputs sample (32 MB in float32; Swin-S has 49.6 M)
+
+
+def snapshot_outputs(model, loss):
+    """What a caller of the timed train step holds after its last step: the loss and the updated parameters -- all of them when
+    they fit DUMP_PARAM_SAMPLE, else a fixed, seeded sample (sorted flat indices into named_parameters() order, the same
+    indices in every run of the same model) -> dict name -> float32 numpy array."""
+    flat = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])
+    if flat.numel() > DUMP_PARAM_SAMPLE:
+        g = torch.Generator().manual_seed(20240229)
+        idx = torch.randint(0, flat.numel(), (DUMP_PARAM_SAMPLE,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    return {"loss": loss.detach().float().reshape(1).cpu().numpy(), "params_sample": flat.cpu().numpy()}
+
+
+def run_workload(model_name, batch, steps, warmup, args, dev, rank, world, snapshot=False):
     """`warmup` untimed + `steps` timed train steps of one workload (barrier + synchronize on both sides, max over ranks);
-    -> dict(value, ms_per_step, workload, roofline)."""
+    -> dict(value, ms_per_step, workload, roofline, outputs).  The per-kernel table / `roofline` (event-sampled steps behind
+    the timed region) only with --full; `outputs` (snapshot_outputs of the last timed step) only when `snapshot`."""
     from vtx import ops
     from vtx.ddp import GradAllReduce
     from vtx.train_step import MixLoss, make_param_groups, train_step
@@ -433,13 +464,14 @@ def run_workload(model_name, batch, steps, warmup, args, dev, rank, world):
         t = torch.tensor([dt], device=dev if dist.get_backend() == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    outputs = snapshot_outputs(model, loss) if snapshot else None      # (before the --full steps below move the parameters on)
     assert torch.isfinite(loss).item(), "non-finite loss"
 
     # The event-sampled step(s) run BEHIND the timed region (round 6): the same step of the same process on the same
     # data, every launch class bracketed with HIP events on its launch stream -- a sampled step records ~1 200 events and runs
     # single-stream (~20 % slower than a timed step), which used to sit inside the K timed steps and cost the headline ~1.2 %.  Every rank
     # runs them (the data-parallel collectives stay matched); rank 0 reads them.
-    timer = None if args.no_kernel_events else ops.KernelTimer()
+    timer = ops.KernelTimer() if args.full and not args.no_kernel_events else None
     nsampled = 0
     step_events = []
     for i in range(max(1, args.event_steps) if timer is not None else 0):
@@ -559,7 +591,7 @@ def run_workload(model_name, batch, steps, warmup, args, dev, rank, world):
                         kernels_sum_ms=round(sum(v["ms"] for v in allk.values()) / nsampled, 3),
                         kernels_sum_over_timed_step=round(sum(v["ms"] for v in allk.values()) / nsampled / (1e3 * dt / steps), 4),
                         kernels=table)
-    return dict(value=value, ms_per_step=1e3 * dt / steps, workload=workload, roofline=roof,
+    return dict(value=value, ms_per_step=1e3 * dt / steps, workload=workload, roofline=roof, outputs=outputs,
                 ddp=dict(active=bool(ddp.active), buckets=len(ddp.buckets), world=ddp.world,
                          reduced_MB=round(sum(b.flat_numel for b in ddp.buckets) * 4 / 2**20, 1)))
 
@@ -573,9 +605,14 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: 128 swin_s / pvt_small, 256 vit_s16, 64 dino)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--optimizer", default="fused", choices=["fused", "torch"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-events", action="store_true")
-    ap.add_argument("--shape-table", default="", help="write the per-(kernel, shape) table of the sampled steps' in-library launches to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, outside the timed region: per-kernel table and "
+                         "`roofline` (event-sampled steps), measured peaks, CPU baseline, `secondary` workloads (Swin-S headline)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's loss and a fixed, seeded sample of the updated parameters to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-events", action="store_true", help="--full: skip the event-sampled steps and the measured peaks")
+    ap.add_argument("--shape-table", default="", help="--full: write the per-(kernel, shape) table of the sampled steps' in-library launches to this file")
     ap.add_argument("--event-steps", type=int, default=1,
                     help="event-sampled steps run BEHIND the timed region (HIP-event brackets around every kernel launch of the step, "
                          "single-stream: the per-kernel table and the `roofline` object come from them; the K timed steps carry no "
@@ -584,7 +621,7 @@ def main():
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--selftest-launch", action="store_true", help="launcher plumbing only (gloo on CPU, no model)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the short ViT-S/16 / PVT-Small / DINO / Twins-SVT-S runs that follow the headline at --gpus 1 (`secondary`)")
+                    help="--full: skip the short ViT-S/16 / PVT-Small / DINO / Twins-SVT-S runs that follow the headline at --gpus 1 (`secondary`)")
     ap.add_argument("--secondary-steps", type=int, default=20)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend of the N > 1 run: nccl (= RCCL, the product path) | gloo (TEST ONLY: lets the "
@@ -599,6 +636,10 @@ def main():
     ap.add_argument("--share-gpu", action="store_true",
                     help="TEST ONLY: every rank uses cuda:(LOCAL_RANK mod device count) -- two ranks on the one GPU of a test box")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.shape_table and not (args.full and not args.no_kernel_events):
+        ap.error("--shape-table comes from the event-sampled steps: it needs --full (and no --no-kernel-events)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)                                     # never returns
@@ -647,16 +688,22 @@ def main():
 
     batch = args.batch or default_batch(args.model)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.model, args.cpu_batch, args.cpu_steps)
         if args.model == "swin_s":
             # SURVEY.md section 8(d) / BASELINE.json cfg-1: ViT-S/16 forward + backward on 32 x 3 x 224 x 224 on the host cores too (~10 s)
             cpu["also"] = [dict(cpu_baseline("vit_s16", args.cpu_batch, args.cpu_steps), model="vit_s16")]
 
     from vtx import functional as VF
-    res = run_workload(args.model, batch, args.steps, args.warmup, args, dev, rank, world)
+    res = run_workload(args.model, batch, args.steps, args.warmup, args, dev, rank, world,
+                       snapshot=bool(args.dump_outputs) and rank == 0)
+    if res["outputs"] is not None:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in res["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), arr)
     secondary = None
-    if world == 1 and not args.no_secondary and args.model == "swin_s" and args.dtype == "bf16":
+    if args.full and world == 1 and not args.no_secondary and args.model == "swin_s" and args.dtype == "bf16":
         # the other BASELINE.json configurations (cfg-2 / 4 / 5) in the same process, after the headline's timed region:
         # ~10 steps each, one event-sampled step; headline keys and timing untouched
         secondary = []
@@ -676,7 +723,7 @@ def main():
                                                                   "avg_launch_us", "launches_per_step", "end_to_end_frac",
                                                                   "executed_flop_frac")}})
     peaks = None
-    if rank == 0 and not args.no_kernel_events:
+    if args.full and rank == 0 and not args.no_kernel_events:
         try:
             peaks = measured_peaks(dev)
             rf = res["roofline"]

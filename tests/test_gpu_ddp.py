@@ -184,7 +184,7 @@ def test_bench_one_gpu_with_the_forced_rccl_group_takes_the_path_of_the_8_gpu_ru
         env.pop(k, None)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--force-ddp", "--batch", "16", "--steps", "3",
-                        "--warmup", "2", "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True, timeout=900, env=env)
+                        "--warmup", "2", "--full", "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
     assert len(lines) == 1, r.stdout[-2000:]

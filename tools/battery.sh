@@ -1,8 +1,10 @@
 #!/bin/bash
 # Round-end measurement battery (run through gpurun from the repo root); outputs under gpurun_out/.
 #   tools/battery.sh prof TAG    tests + rocprofv3 kernel stats (4 workloads) + PMC traffic (3 models) + micro-benchmarks
-#   tools/battery.sh bench       the bench.py lines of the 4 workloads (run AFTER the PMC json files were copied to profiles/)
+#   tools/battery.sh bench       the `bench.py --full` lines of the 5 workloads into $OUT (default out/; run AFTER the PMC json
+#                                files were copied to profiles/)
 R=$PWD
+OUT=${OUT:-$R/out}
 export TMPDIR=/tmp
 case "$1" in
   prof)
@@ -21,9 +23,10 @@ case "$1" in
     [ -x tools/probe/store_pattern.bin ] || hipcc --offload-arch=gfx950 -O3 -o tools/probe/store_pattern.bin tools/probe/store_pattern.hip > /dev/null 2>&1
     timeout 120 tools/probe/store_pattern.bin > gpurun_out/store_pattern.log 2>&1 ;;
   bench)
-    timeout 900 python bench.py --steps 20 --warmup 5 2>&1 | grep '"metric"' > gpurun_out/bench_swin_s.log
-    for m in vit_s16 pvt_small; do timeout 900 python bench.py --model $m --steps 20 --warmup 5 2>&1 | grep '"metric"' > gpurun_out/bench_$m.log; done
-    timeout 900 python bench.py --model dino --steps 10 --warmup 3 --cpu-batch 2 --cpu-steps 1 2>&1 | grep '"metric"' > gpurun_out/bench_dino.log
-    timeout 900 python bench.py --model twins_svt_s --steps 20 --warmup 5 --no-cpu-baseline --no-secondary 2>&1 | grep '"metric"' > gpurun_out/bench_twins_svt_s.log
-    for m in swin_s vit_s16 pvt_small dino twins_svt_s; do cut -c1-260 gpurun_out/bench_$m.log; done ;;
+    mkdir -p "$OUT"
+    timeout 900 python bench.py --full --steps 20 --warmup 5 2>&1 | grep '"metric"' > "$OUT/bench_swin_s.log"
+    for m in vit_s16 pvt_small; do timeout 900 python bench.py --full --model $m --steps 20 --warmup 5 2>&1 | grep '"metric"' > "$OUT/bench_$m.log"; done
+    timeout 900 python bench.py --full --model dino --steps 10 --warmup 3 --cpu-batch 2 --cpu-steps 1 2>&1 | grep '"metric"' > "$OUT/bench_dino.log"
+    timeout 900 python bench.py --full --model twins_svt_s --steps 20 --warmup 5 --no-cpu-baseline --no-secondary 2>&1 | grep '"metric"' > "$OUT/bench_twins_svt_s.log"
+    for m in swin_s vit_s16 pvt_small dino twins_svt_s; do cut -c1-260 "$OUT/bench_$m.log"; done ;;
 esac

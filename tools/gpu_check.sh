@@ -2,6 +2,7 @@
 # Standard GPU battery (run through gpurun from the repo root):  tools/gpu_check.sh [tests] [bench] [prof TAG]
 set -u
 R=$PWD
+OUT=${OUT:-$R/out}          # the bench / benchq lines
 mkdir -p gpurun_out
 for what in "$@"; do
   case "$what" in
@@ -9,9 +10,11 @@ for what in "$@"; do
       rm -f gpurun_out/parity.log
       timeout 1500 python -m pytest tests -q -m gpu -x --timeout 900 2>&1 | tail -15 | tee gpurun_out/tests.log ;;
     bench)
-      timeout 900 python bench.py --steps 20 --warmup 5 2>&1 | grep -v amdgpu.ids | tail -3 | tee gpurun_out/bench.log ;;
+      mkdir -p "$OUT"
+      timeout 900 python bench.py --full --steps 20 --warmup 5 2>&1 | grep -v amdgpu.ids | tail -3 | tee "$OUT/bench.log" ;;
     benchq)
-      timeout 900 python bench.py --steps 10 --warmup 3 --no-cpu-baseline 2>&1 | grep -v amdgpu.ids | tail -3 | tee gpurun_out/benchq.log ;;
+      mkdir -p "$OUT"
+      timeout 900 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline 2>&1 | grep -v amdgpu.ids | tail -3 | tee "$OUT/benchq.log" ;;
     profpvt:*)
       tag=${what#profpvt:}
       mkdir -p gpurun_out/profpvt_${tag}

@@ -13,12 +13,14 @@ assembly hipcc generates (no GPU needed).  Every gemm_astat_kernel instantiation
 
     python tools/probe/scan_astat_isa.py        exit status 1 on a violation
 """
-import os, re, subprocess, sys
+import atexit, os, re, shutil, subprocess, sys, tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SRC = os.path.join(REPO, "vision-transformers-pytorch_amd", "csrc", "gemm_astat.hip")
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "vision-transformers-pytorch_amd"))
 from vtx.build import FLAGS   # the flags of the shipped library: a scan validates THAT binary
+TMP = tempfile.mkdtemp(prefix="vtx_scan_")     # this run's own: fixed /tmp names are shared by every user and checkout of a machine
+atexit.register(shutil.rmtree, TMP, True)
 RESERVED0 = 224 if any(a.startswith("-DAS_NCWD=4") for a in sys.argv[1:]) else 152
 
 
@@ -30,7 +32,7 @@ def vgprs(line):
 
 
 def main():
-    out = "/tmp/scan_gemm_astat.s"
+    out = os.path.join(TMP, "scan_gemm_astat.s")
     r = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + [a for a in sys.argv[1:] if a.startswith("-")] + ["-S", "--cuda-device-only", "-o", out, SRC],
                        capture_output=True, text=True)
     if r.returncode:

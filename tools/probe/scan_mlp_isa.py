@@ -13,12 +13,14 @@ Other variant codes (tests / timing probes: 16 waves, z / h outputs at 12 waves)
 
     python tools/probe/scan_mlp_isa.py        exit status 1 on a violation
 """
-import os, re, subprocess, sys
+import atexit, os, re, shutil, subprocess, sys, tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SRC = os.path.join(REPO, "vision-transformers-pytorch_amd", "csrc", "mlp_fused.hip")
 sys.path.insert(0, os.path.join(REPO, "vision-transformers-pytorch_amd"))
 from vtx.build import FLAGS   # the flags of the shipped library: a scan validates THAT binary
+TMP = tempfile.mkdtemp(prefix="vtx_scan_")     # this run's own: fixed /tmp names are shared by every user and checkout of a machine
+atexit.register(shutil.rmtree, TMP, True)
 
 # (kernel, KS, WAVES, rest of the template list as mangled by hipcc)
 DEFAULTS = [("mlp_fwd_kernel", ks, 12, f"Lb0ELb0ELb{lnf}EE") for ks in (2, 3) for lnf in (0, 1)] + \
@@ -27,7 +29,7 @@ DEFAULTS = [("mlp_fwd_kernel", ks, 12, f"Lb0ELb0ELb{lnf}EE") for ks in (2, 3) fo
 
 
 def main():
-    out = "/tmp/scan_mlp_fused.s"
+    out = os.path.join(TMP, "scan_mlp_fused.s")
     r = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["-S", "--cuda-device-only", "-o", out, SRC], capture_output=True, text=True)
     if r.returncode:
         print("COMPILE FAILED:", r.stderr[-500:])

@@ -6,13 +6,15 @@ overlapped another kernel (tools/probe/merge_bisect.py).
 
     python tools/probe/scan_pk_hazard.py [-D...]        exit status 1 if any site is found
 """
-import os, re, subprocess, sys
+import atexit, os, re, shutil, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CSRC = os.path.join(REPO, "vision-transformers-pytorch_amd", "csrc")
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "vision-transformers-pytorch_amd"))
 from vtx.build import FLAGS   # the flags of the shipped library: a scan validates THAT binary
+TMP = tempfile.mkdtemp(prefix="vtx_scan_")     # this run's own: fixed /tmp names are shared by every user and checkout of a machine
+atexit.register(shutil.rmtree, TMP, True)
 MEM = ("ds_", "global_", "buffer_", "flat_", "scratch_")
 
 
@@ -28,7 +30,7 @@ def regs(tok):
 
 
 def scan(path, extra):
-    out = f"/tmp/scan_{os.path.basename(path)}.s"
+    out = os.path.join(TMP, f"scan_{os.path.basename(path)}.s")
     r = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + extra + ["-S", "--cuda-device-only", "-o", out, path], capture_output=True, text=True)
     if r.returncode:
         return [(path, 0, "COMPILE FAILED: " + r.stderr[-300:], "")]

@@ -12,16 +12,18 @@ assembly hipcc generates (no GPU needed):
 
     python tools/probe/scan_wgrad_isa.py        exit status 1 on a violation
 """
-import os, re, subprocess, sys
+import atexit, os, re, shutil, subprocess, sys, tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SRC = os.path.join(REPO, "vision-transformers-pytorch_amd", "csrc", "gemm_wgrad_glds.hip")
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "vision-transformers-pytorch_amd"))
 from vtx.build import FLAGS   # the flags of the shipped library: a scan validates THAT binary
+TMP = tempfile.mkdtemp(prefix="vtx_scan_")     # this run's own: fixed /tmp names are shared by every user and checkout of a machine
+atexit.register(shutil.rmtree, TMP, True)
 
 
 def main():
-    out = "/tmp/scan_wgrad_wide.s"
+    out = os.path.join(TMP, "scan_wgrad_wide.s")
     r = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["-S", "--cuda-device-only", "-o", out, SRC], capture_output=True, text=True)
     if r.returncode:
         print("COMPILE FAILED:", r.stderr[-500:])

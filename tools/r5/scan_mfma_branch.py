@@ -6,18 +6,22 @@ code, but not when the read sits at the head of the branch target: a chain of v_
 returned the accumulator before the chain had drained (fp32 attention, 10 key tiles).
 
     python tools/r5/scan_mfma_branch.py [file.s ...]        exit status 1 if any site is found
-Without arguments: compiles csrc/*.hip with the library's flags (or reuses /tmp/scan_<file>.s of tools/probe/scan_pk_hazard.py
-when newer than the sources)."""
+Without arguments: compiles csrc/*.hip with the library's flags into a temporary directory of its own."""
+import atexit
 import os
 import re
+import shutil
 import subprocess
 import sys
+import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CSRC = os.path.join(REPO, "vision-transformers-pytorch_amd", "csrc")
 sys.path.insert(0, os.path.join(REPO, "vision-transformers-pytorch_amd"))
 from vtx.build import FLAGS   # the flags of the shipped library: a scan validates THAT binary
+TMP = tempfile.mkdtemp(prefix="vtx_scan_")     # this run's own: fixed /tmp names are shared by every user and checkout of a machine
+atexit.register(shutil.rmtree, TMP, True)
 
 LOOK_BACK, LOOK_AHEAD = 12, 12
 MIN_GAP = 6           # issue slots between the MFMA and the first reader on the taken path (s_nop N counts N + 1): the proven failure
@@ -116,10 +120,7 @@ def scan_file(path):
 
 
 def isa_of(src):
-    out = f"/tmp/scan_{os.path.basename(src)}.s"
-    deps = [src] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    if os.path.exists(out) and os.path.getmtime(out) > max(os.path.getmtime(d) for d in deps):
-        return out
+    out = os.path.join(TMP, f"scan_{os.path.basename(src)}.s")
     r = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["-S", "--cuda-device-only", "-o", out, src], capture_output=True, text=True)
     if r.returncode:
         raise RuntimeError(f"hipcc failed for {src}: {r.stderr[-300:]}")
