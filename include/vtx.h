@@ -541,6 +541,31 @@ size_t vtx_randaug_plan_bytes(void);
 int vtx_randaug_max_ops(void);
 int vtx_randaug_apply(const void* x, const void* plan, void* scratch, void* out, int N, int C, int H, int W, void* stream);
 
+/* ---- Crop + BICUBIC resize + flip on the device (csrc/resample.hip): RandomResizedCrop(size,
+ * BICUBIC) + RandomHorizontalFlip of reference factory.py:170-171 (and the crops of DINOAugment, transforms.py:249-279) and
+ * Resize + CenterCrop of factory.py:215-222, bit-exact to PIL's 8-bit resample of the CROPPED image (img.crop(box).resize(
+ * size, BICUBIC): filter windows clamp at the crop's edges).  All random draws are made on the host
+ * (vtx.input_pipeline.RandomResizedCropPlan); table = device array of M records, one per OUTPUT image (several may name one
+ * source):
+ *   {int64 src_off (byte offset of the source's row 0 in buf); int src_h, src_w, stride (bytes per source row);
+ *    int top, left, ch, cw (crop rectangle); int res_h, res_w (size the crop is resampled to);
+ *    int win_top, win_left (out = rows [win_top, win_top + S_h) x columns [win_left, win_left + S_w) of the resampled image:
+ *    0, 0 and res = S for a plain resized crop; the CenterCrop offsets for Resize + CenterCrop); int flip; int pad}
+ *   (vtx_resample_plan_bytes() = 64 bytes each).
+ * buf: buf_bytes device bytes, the sources in PIL's layout (H x W x 3 uint8, RGB interleaved); ws: device workspace of
+ * vtx_resample_workspace_bytes(M, S_h, S_w) bytes (the coefficient tables, built on the device); out: [M, 3, S_h, S_w]
+ * uint8 -- what vtx_randaug_apply and vtx_mix_normalize_erase take.  Supported: crop side / output side <= 16 on both axes
+ * (at most vtx_resample_max_taps() = 65 filter taps), up-scaling included, 3 * S_w <= ~2500.  A record outside that range,
+ * outside its source or outside buf is the caller's error: its image is zero-filled, nothing of it is read.
+ * vtx_resample_coeffs: the tables of one axis (length L resampled to S, outputs [first, first + n)) as the kernel builds them:
+ *   table = (2 + max_taps) * n device int32:  xmin[n] | count[n] | coef[max_taps][n]  (22-bit fixed point, unused taps 0). */
+size_t vtx_resample_plan_bytes(void);
+int vtx_resample_max_taps(void);
+size_t vtx_resample_workspace_bytes(int M, int S_h, int S_w);
+int vtx_resample_coeffs(int L, int S, int first, int n, void* table, void* stream);
+int vtx_resized_crop(const void* buf, size_t buf_bytes, const void* table, void* ws, size_t ws_bytes, void* out, int M, int S_h,
+                     int S_w, void* stream);
+
 /* ---- Fused optimizer tail (csrc/optim.hip): nn.utils.clip_grad_norm_ + torch.optim.AdamW.step of the reference's
  * train step (train.py:285-299) as two multi-tensor passes.  Tensors are given as HOST arrays of n device pointers
  * (fp32, any 4-byte alignment) and element counts; the addresses travel in kernel arguments (64 tensors per launch).

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VTX_LIBVTX") or os.path.join(_HERE, "libvtx.so")   # (override: A/B of two builds on one box)
 
 F32, BF16 = 0, 1
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 
 class VtxError(RuntimeError):
@@ -203,6 +203,11 @@ _SIGNATURES = {
     "vtx_randaug_plan_bytes": (c_size_t, []),
     "vtx_randaug_max_ops": (c_int, []),
     "vtx_randaug_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "vtx_resample_plan_bytes": (c_size_t, []),
+    "vtx_resample_max_taps": (c_int, []),
+    "vtx_resample_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "vtx_resample_coeffs": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "vtx_resized_crop": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_void_p]),
     "vtx_ema_update": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p]),
     "vtx_dino_loss_workspace": (c_size_t, [c_int, c_int]),
     "vtx_dino_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int,

@@ -13,6 +13,12 @@ pixel work moves to the device.  The "dataset" a partner is drawn from is the ba
 With ``randaug=RandAugmentPlan(...)`` the pipeline follows the reference's default ``mix_before_aug`` order on uint8
 images (factory.py:184-187): PIL-style mix (``Image.blend`` / ``paste``), RandAugment (autoaugment.py:586-678, every op
 bit-exact to PIL; csrc/randaug.hip), then ToTensor / Normalize / RandomErasing as before.
+
+With ``crop=RandomResizedCropPlan(...)`` the pipeline starts from the DECODED images (a list of H x W x 3 uint8 arrays of
+any size): RandomResizedCrop(size, BICUBIC) + RandomHorizontalFlip (factory.py:170-171) run on the device
+(csrc/resample.hip, bit-exact to PIL's ``crop`` + ``resize``), fed by one asynchronous upload of the crops' pixels.
+``DeviceEvalPipeline`` is the validation transform (Resize + CenterCrop + ToTensor + Normalize, factory.py:215-222) and
+``DeviceMultiCrop`` the crop stage of DINOAugment (transforms.py:249-279) on the same kernel.
 """
 import math
 import random as _random
@@ -250,7 +256,277 @@ class RandAugmentPlan:
         return code, p, f
 
 
-class DeviceMixPipeline:
+MAX_TAPS = 65                                     # = vtx_resample_max_taps(): crop side / output side <= 16
+MAX_OUT_WIDTH = 840                               # the LDS tile of csrc/resample.hip holds 65 rows of the output's width
+
+
+def resample_taps(length, size):
+    """PIL's ksize of one axis: ``length`` source pixels resampled to ``size`` (BICUBIC, support 2)."""
+    return int(math.ceil(2.0 * max(length / size, 1.0))) * 2 + 1
+
+
+def _hw(size):
+    return (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+
+
+class RandomResizedCropPlan:
+    """Host side of torchvision's ``RandomResizedCrop(size, scale, ratio, interpolation=BICUBIC)`` followed by
+    ``RandomHorizontalFlip(flip_p)`` (reference factory.py:170-171; DINOAugment's crops with ``flip_p=0``).  ``draw``
+    makes torchvision's random calls in torchvision's order on ``generator`` (None = torch's global one, which is what
+    torchvision consumes): up to 10 attempts of ``torch.empty(1).uniform_`` for the area fraction and for the log-ratio
+    (between float32 logs of ``ratio``), ``torch.randint`` for top then left of an attempt that fits; after 10 misses the
+    ratio-clamped centre crop; then ``torch.rand(1) < flip_p``.  torchvision is not installed where this was written, so
+    the restatement of ``get_params`` was NOT checked against it; ``draw`` is replaceable -- every pipeline also takes
+    the boxes explicitly.  Only BICUBIC on 3-channel uint8 images is built: ``interpolation`` may be "bicubic", PIL's
+    ``Image.BICUBIC`` (the integer 3) or torchvision's ``InterpolationMode.BICUBIC`` (whose value is "bicubic"); anything
+    else raises."""
+
+    def __init__(self, size, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), flip_p=0.5, generator=None, interpolation="bicubic"):
+        mode = getattr(interpolation, "value", interpolation)     # an enum member (PIL's Resampling, torchvision's InterpolationMode)
+        if not (mode == 3 or (isinstance(mode, str) and mode.lower() == "bicubic")):
+            raise ValueError(f"RandomResizedCropPlan: only BICUBIC is built, got interpolation={interpolation!r}")
+        self.out_hw = _hw(size)
+        if min(self.out_hw) < 1 or self.out_hw[1] > MAX_OUT_WIDTH:
+            raise ValueError(f"RandomResizedCropPlan: output size {self.out_hw} outside 1..{MAX_OUT_WIDTH} columns")
+        self.scale, self.ratio, self.flip_p, self.generator = tuple(scale), tuple(ratio), flip_p, generator
+        log_ratio = torch.log(torch.tensor(self.ratio))           # float32, as torchvision computes it
+        self._log_ratio = (float(log_ratio[0]), float(log_ratio[1]))
+        self.fallback = False                                     # whether the last draw took the centre fallback
+
+    def draw(self, h, w):
+        """-> (top, left, crop_h, crop_w, flip) for one decoded image of h x w."""
+        g = self.generator
+        area = h * w
+        box = None
+        for _ in range(10):
+            target_area = area * torch.empty(1).uniform_(self.scale[0], self.scale[1], generator=g).item()
+            aspect = torch.exp(torch.empty(1).uniform_(self._log_ratio[0], self._log_ratio[1], generator=g)).item()
+            cw = int(round(math.sqrt(target_area * aspect)))
+            ch = int(round(math.sqrt(target_area / aspect)))
+            if 0 < cw <= w and 0 < ch <= h:
+                top = torch.randint(0, h - ch + 1, size=(1,), generator=g).item()
+                left = torch.randint(0, w - cw + 1, size=(1,), generator=g).item()
+                box = (top, left, ch, cw)
+                break
+        self.fallback = box is None
+        if box is None:
+            in_ratio = float(w) / float(h)
+            if in_ratio < min(self.ratio):
+                cw = w
+                ch = int(round(cw / min(self.ratio)))
+            elif in_ratio > max(self.ratio):
+                ch = h
+                cw = int(round(ch * max(self.ratio)))
+            else:
+                cw, ch = w, h
+            box = ((h - ch) // 2, (w - cw) // 2, ch, cw)
+        flip = bool(torch.rand(1, generator=g).item() < self.flip_p)
+        return box + (flip,)
+
+    def record(self, h, w, box=None, source=0):
+        """The crop record of one image: ``box`` = (top, left, crop_h, crop_w, flip) or None to draw it."""
+        top, left, ch, cw, flip = box if box is not None else self.draw(h, w)
+        return dict(source=source, box=(int(top), int(left), int(ch), int(cw)), res=self.out_hw, window=(0, 0), flip=bool(flip))
+
+
+class CenterCropPlan:
+    """``transforms.Resize(resize, BICUBIC)`` + ``transforms.CenterCrop(valid_size)`` (reference factory.py:215-222,
+    ``resize = valid_size + 32``): the shorter edge goes to ``resize``, the longer one to int(resize * long / short); the
+    crop starts at int(round((side - valid_size) / 2.0)).  Only the pixels inside the crop window of the full-image
+    resample are computed (bit-identical to resizing everything and cropping)."""
+
+    def __init__(self, valid_size, resize=None):
+        self.valid_size = int(valid_size)
+        self.resize = int(resize) if resize is not None else self.valid_size + 32
+        self.out_hw = (self.valid_size, self.valid_size)
+        if self.valid_size < 1 or self.valid_size > MAX_OUT_WIDTH or self.resize < self.valid_size:
+            raise ValueError(f"CenterCropPlan: valid_size {valid_size} / resize {resize}: need 1 <= valid_size <= resize "
+                             f"(CenterCrop's zero padding of a smaller image is not built) and at most {MAX_OUT_WIDTH} columns")
+
+    def geometry(self, h, w):
+        """-> (resized_h, resized_w, crop_top, crop_left)"""
+        if w <= h:
+            nw, nh = self.resize, int(self.resize * h / w)
+        else:
+            nh, nw = self.resize, int(self.resize * w / h)
+        return nh, nw, int(round((nh - self.valid_size) / 2.0)), int(round((nw - self.valid_size) / 2.0))
+
+    def record(self, h, w, box=None, source=0):
+        nh, nw, top, left = self.geometry(h, w)
+        return dict(source=source, box=(0, 0, h, w), res=(nh, nw), window=(top, left), flip=False)
+
+
+def check_crop_record(rec, h, w, out_hw):
+    """Raises VtxError for a record outside what csrc/resample.hip computes exactly (it never produces other bits)."""
+    top, left, ch, cw = rec["box"]
+    (rh, rw), (wt, wl) = rec["res"], rec["window"]
+    if ch < 1 or cw < 1 or top < 0 or left < 0 or top + ch > h or left + cw > w:
+        raise ops.VtxError(f"vtx: crop box (top {top}, left {left}, {ch} x {cw}) outside the {h} x {w} image")
+    if rh < 1 or rw < 1 or wt < 0 or wl < 0 or wt + out_hw[0] > rh or wl + out_hw[1] > rw:
+        raise ops.VtxError(f"vtx: output window {out_hw} at ({wt}, {wl}) outside the resampled {rh} x {rw} image")
+    if resample_taps(ch, rh) > MAX_TAPS or resample_taps(cw, rw) > MAX_TAPS:
+        raise ops.VtxError(f"vtx: crop {ch} x {cw} -> {rh} x {rw}: down-scaling by more than 16 on an axis is not built")
+
+
+def pack_sources(images, records, alloc=None):
+    """Pack the pixels the crops read into one byte buffer: per source image the bounding rectangle of the boxes that name
+    it (a source no record names takes no room), rows contiguous.  ``alloc(nbytes)`` -> uint8 host tensor to fill (a pinned
+    staging buffer); default a fresh tensor.  -> (buffer, placed) with placed[s] = (offset, row0, col0, rows, cols)."""
+    rects = {}
+    for rec in records:
+        s = rec["source"]
+        top, left, ch, cw = rec["box"]
+        r = rects.get(s)
+        rects[s] = (top, left, top + ch, left + cw) if r is None else (min(r[0], top), min(r[1], left), max(r[2], top + ch),
+                                                                     max(r[3], left + cw))
+    placed, total = {}, 0
+    for s in sorted(rects):
+        r0, c0, r1, c1 = rects[s]
+        placed[s] = (total, r0, c0, r1 - r0, c1 - c0)
+        total += (r1 - r0) * (c1 - c0) * 3
+    buf = alloc(total) if alloc is not None else torch.empty(total, dtype=torch.uint8)
+    for s, (off, r0, c0, rows, cols) in placed.items():
+        buf[off:off + rows * cols * 3].view(rows, cols, 3).copy_(images[s][r0:r0 + rows, c0:c0 + cols])
+    return buf[:total], placed
+
+
+def pack_crop_table(records, placed):
+    """-> uint8 [M * vtx_resample_plan_bytes()]: one record per output image (csrc/resample.hip RsRec), addressing the
+    buffer ``pack_sources`` laid out."""
+    recs = []
+    for rec in records:
+        off, r0, c0, rows, cols = placed[rec["source"]]
+        top, left, ch, cw = rec["box"]
+        recs.append(struct.pack("<q13i4x", off, rows, cols, cols * 3, top - r0, left - c0, ch, cw, *rec["res"], *rec["window"],
+                                int(rec["flip"]), 0))
+    return torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8)
+
+
+def _as_images(images):
+    """list of H x W x 3 uint8 host arrays / tensors -> list of tensors; raises for anything else."""
+    out = []
+    for im in images:
+        t = torch.as_tensor(im)
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.is_cuda or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ops.VtxError(f"vtx: the crop stage takes decoded H x W x 3 uint8 host images (PIL's RGB layout), got "
+                               f"{t.dtype} {tuple(t.shape)}")
+        out.append(t)
+    if not out:
+        raise ops.VtxError("vtx: empty batch of images")
+    return out
+
+
+def pack_mix_plans(plans, fmode=0):
+    """plans of plan_batch -> (plan table uint8 [N * vtx_mix_plan_bytes()], fill table fp32 or None); ``fmode``: the erase
+    colour mode (ErasePlan.fmode)."""
+    maxr = ops.mix_max_rects()
+    recs, fills, foff = [], [], 0
+    for p in plans:
+        rects = p["rects"]
+        if len(rects) > maxr:
+            raise ops.VtxError(f"vtx: at most {maxr} erase rectangles per image")
+        rr = [r[:4] for r in rects] + [(0, 0, 0, 0)] * (maxr - len(rects))
+        offs = [0] * maxr
+        for i, r in enumerate(rects):
+            if fmode and r[4] is not None:
+                offs[i] = foff
+                fills.append(r[4].reshape(-1))
+                foff += r[4].numel()
+        x1, y1, x2, y2 = p["box"]
+        recs.append(struct.pack("<iifiiiii4i4i4h4hi4i", p["partner"], p["mode"], p["ratio"], x1, y1, x2, y2, len(rects),
+                                *[r[0] for r in rr], *[r[1] for r in rr], *[r[2] for r in rr], *[r[3] for r in rr],
+                                fmode, *offs))
+    assert len(recs[0]) == ops.mix_plan_bytes()
+    table = torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8)
+    return table, (torch.cat(fills) if fills else None)
+
+
+def identity_plans(n):
+    """The trivial plans of n images: no mix, no rectangles (ToTensor + Normalize only)."""
+    return [dict(partner=k, mode=0, ratio=1.0, box=(0, 0, 0, 0), rects=[]) for k in range(n)]
+
+
+class _UploadRing:
+    """Host -> device copies that do not stall the host: rings of 4 pinned buffers, each guarded by an event."""
+
+    def __init__(self):
+        self._ring, self._slot = {}, {}           # pinned staging buffers (asynchronous uploads), per table kind
+
+    def _pinned(self, n, dtype, kind):
+        ring = self._ring.get(kind)
+        if not ring or ring[0][0].numel() < n or ring[0][0].dtype != dtype:
+            cap = max(n, 2 * (ring[0][0].numel() if ring else 0))
+            ring = self._ring[kind] = [(torch.empty(cap, dtype=dtype).pin_memory(), torch.cuda.Event()) for _ in range(4)]
+            self._slot[kind] = 0
+            for _, ev in ring:
+                ev.record()
+        buf, ev = ring[self._slot[kind]]
+        self._slot[kind] = (self._slot[kind] + 1) % len(ring)
+        ev.synchronize()                          # the copy issued 4 calls ago has long finished
+        return buf, ev
+
+    def upload(self, host, dev, kind="plan"):
+        """Host table -> device without stalling the host: a pageable host-to-device copy would serialise the host with
+        the GPU stream every step; a ring of 4 pinned buffers (each guarded by an event) keeps the copy asynchronous."""
+        n = host.numel()
+        buf, ev = self._pinned(n, host.dtype, kind)
+        buf[:n].copy_(host)
+        out = buf[:n].to(dev, non_blocking=True)
+        ev.record()
+        return out
+
+
+class _CropStage(_UploadRing):
+    """The crop stage the pipelines share: validate, pack and upload the pixels the crops read, launch the resample.
+    ``crop_records`` holds the records of the last call (boxes, flips), ``upload_bytes`` the size of its upload."""
+
+    def __init__(self):
+        super().__init__()
+        self.crop_records, self.upload_bytes = [], 0
+
+    def upload_crops(self, images, records, dev):
+        """Validate the records, pack the pixels they read straight into a pinned staging buffer, one asynchronous upload
+        -> (device buffer, placed).  Raises before anything is launched."""
+        for rec in records:
+            h, w = images[rec["source"]].shape[:2]
+            check_crop_record(rec, h, w, rec["out_hw"])
+        slot = []
+
+        def alloc(nbytes):
+            slot.extend(self._pinned(max(nbytes, 1), torch.uint8, "images"))
+            return slot[0]
+
+        host, placed = pack_sources(images, records, alloc)
+        buf = host.to(dev, non_blocking=True)
+        slot[1].record()
+        self.upload_bytes = host.numel()
+        return buf, placed
+
+    def run_crops(self, images, plans, dev, boxes=None):
+        """The crop stage shared by the pipelines: ``plans`` = one plan per crop of every image (all images get the same
+        list); ``boxes[k][j]`` = the explicit box of image k, crop j (None: drawn, image by image, crop by crop).
+        -> list of uint8 (N, 3, S_h, S_w) device tensors, one per plan; one upload, one launch per distinct output size."""
+        images = _as_images(images)
+        records = []
+        for k, im in enumerate(images):
+            for j, plan in enumerate(plans):
+                rec = plan.record(im.shape[0], im.shape[1], None if boxes is None else boxes[k][j], source=k)
+                rec["out_hw"], rec["plan"] = plan.out_hw, j
+                records.append(rec)
+        buf, placed = self.upload_crops(images, records, dev)
+        self.crop_records = records
+        out = [None] * len(plans)
+        for hw in sorted({p.out_hw for p in plans}):
+            js = [j for j, p in enumerate(plans) if p.out_hw == hw]
+            recs = [r for j in js for r in records if r["plan"] == j]          # plan-major: each plan's batch is contiguous
+            table = self.upload(pack_crop_table(recs, placed), dev, "crops")
+            res = ops.resized_crop(buf, table, hw)
+            for i, j in enumerate(js):
+                out[j] = res[i * len(images):(i + 1) * len(images)]
+        return out
+
+
+class DeviceMixPipeline(_CropStage):
     """batch (N, C, H, W) uint8 or fp32 on the GPU + labels (N,)  ->  (normalised batch, label1, label2, ratio): the tuple
     the reference's train step consumes (train.py:270-272).  ``output``: "nchw_fp32" (the reference's model input) or
     "nhwc_bf16" -- a bf16 tensor of shape (N, C, H, W) in channels-last memory that the HIP models' patch gathers read
@@ -259,44 +535,29 @@ class DeviceMixPipeline:
     ``randaug``: a RandAugmentPlan.  The batch must then be uint8 RGB; each sample is mixed as PIL images
     (``Image.blend`` / ``paste``), put through RandAugment (both in csrc/randaug.hip, bit-exact to PIL) and then
     normalised and erased by the same kernel as without it.  Only the reference's default ``mix_before_aug=True`` order
-    is built (augmenting before the mix needs two independent augmentations per sample)."""
+    is built (augmenting before the mix needs two independent augmentations per sample).
+
+    ``crop``: a RandomResizedCropPlan.  ``images`` is then a list of decoded H x W x 3 uint8 host arrays or tensors of any
+    sizes; the pixels the crops read are packed into a pinned buffer and uploaded once, cropped / resized / flipped on the
+    device (csrc/resample.hip, bit-exact to PIL) into the uint8 batch, and the sequence above runs on that batch.  The
+    crops of a batch are drawn first, image by image (``boxes`` = [(top, left, h, w, flip)] overrides the draws)."""
 
     def __init__(self, mixup=0.2, cutmix=1, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), erase=None, seed=None,
-                 output="nchw_fp32", randaug=None, mix_before_aug=True):
+                 output="nchw_fp32", randaug=None, mix_before_aug=True, crop=None):
         if output not in ("nchw_fp32", "nhwc_bf16"):
             raise ValueError(output)
         if randaug is not None and not mix_before_aug:
             raise NotImplementedError("DeviceMixPipeline: randaug with mix_before_aug=False (augment each image before the "
                                       "mix) is not built; the reference's default is mix_before_aug=True")
         self.mixup, self.cutmix, self.erase, self.output = mixup, cutmix, erase, output
-        self.randaug = randaug
+        self.randaug, self.crop = randaug, crop
         self.mean, self.std = torch.tensor(mean, dtype=torch.float32), torch.tensor(std, dtype=torch.float32)
         self.rng = _random.Random(seed) if seed is not None else _random
-        self._ring, self._slot = {}, {}           # pinned staging buffers (asynchronous uploads), per table kind
+        super().__init__()
 
     def pack(self, plans):
         """-> (plan table uint8 [N * vtx_mix_plan_bytes()], fill table fp32 or None)"""
-        maxr = ops.mix_max_rects()
-        fmode = self.erase.fmode if self.erase is not None else 0
-        recs, fills, foff = [], [], 0
-        for p in plans:
-            rects = p["rects"]
-            if len(rects) > maxr:
-                raise ops.VtxError(f"vtx: at most {maxr} erase rectangles per image")
-            rr = [r[:4] for r in rects] + [(0, 0, 0, 0)] * (maxr - len(rects))
-            offs = [0] * maxr
-            for i, r in enumerate(rects):
-                if fmode and r[4] is not None:
-                    offs[i] = foff
-                    fills.append(r[4].reshape(-1))
-                    foff += r[4].numel()
-            x1, y1, x2, y2 = p["box"]
-            recs.append(struct.pack("<iifiiiii4i4i4h4hi4i", p["partner"], p["mode"], p["ratio"], x1, y1, x2, y2, len(rects),
-                                    *[r[0] for r in rr], *[r[1] for r in rr], *[r[2] for r in rr], *[r[3] for r in rr],
-                                    fmode, *offs))
-        assert len(recs[0]) == ops.mix_plan_bytes()
-        table = torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8)
-        return table, (torch.cat(fills) if fills else None)
+        return pack_mix_plans(plans, self.erase.fmode if self.erase is not None else 0)
 
     def pack_randaug(self, plans):
         """-> uint8 [N * vtx_randaug_plan_bytes()]: per sample the PIL-style mix and the encoded RandAugment ops
@@ -316,26 +577,11 @@ class DeviceMixPipeline:
         assert len(recs[0]) == ops.randaug_plan_bytes()
         return torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8)
 
-    def upload(self, host, dev, kind="plan"):
-        """Host table -> device without stalling the host: a pageable host-to-device copy would serialise the host with
-        the GPU stream every step; a ring of 4 pinned buffers (each guarded by an event) keeps the copy asynchronous."""
-        n = host.numel()
-        ring = self._ring.get(kind)
-        if not ring or ring[0][0].numel() < n or ring[0][0].dtype != host.dtype:
-            cap = max(n, 2 * (ring[0][0].numel() if ring else 0))
-            ring = self._ring[kind] = [(torch.empty(cap, dtype=host.dtype).pin_memory(), torch.cuda.Event()) for _ in range(4)]
-            self._slot[kind] = 0
-            for _, ev in ring:
-                ev.record()
-        buf, ev = ring[self._slot[kind]]
-        self._slot[kind] = (self._slot[kind] + 1) % len(ring)
-        ev.synchronize()                          # the copy issued 4 calls ago has long finished
-        buf[:n].copy_(host)
-        out = buf[:n].to(dev, non_blocking=True)
-        ev.record()
-        return out
-
-    def __call__(self, images, labels, indices=None):
+    def __call__(self, images, labels, indices=None, boxes=None):
+        if self.crop is not None:
+            images = self.run_crops(images, [self.crop], labels.device, None if boxes is None else [[b] for b in boxes])[0]
+        elif boxes is not None:
+            raise ops.VtxError("vtx: boxes given to a pipeline without a crop plan")
         n, c, h, w = images.shape
         if self.randaug is not None and (images.dtype != torch.uint8 or c != 3):
             raise ops.VtxError(f"vtx: RandAugment works on uint8 RGB images (PIL's), got {images.dtype} with {c} channels")
@@ -354,3 +600,43 @@ class DeviceMixPipeline:
         out = ops.mix_normalize_erase(images, plan, self.mean, self.std, fills, nhwc_bf16=self.output == "nhwc_bf16")
         ratio = torch.tensor([p["label_ratio"] for p in plans], dtype=torch.float32, device=dev)
         return out, labels, labels[partner], ratio
+
+
+class DeviceEvalPipeline(_CropStage):
+    """The reference's validation transform (factory.py:215-222) from decoded images: Resize(valid_size + 32, BICUBIC) +
+    CenterCrop(valid_size) on the device (csrc/resample.hip, bit-exact to PIL), then ToTensor + Normalize by the kernel of
+    the training pipeline with a trivial plan (no mix, no rectangles).  list of H x W x 3 uint8 host images -> the
+    normalised batch, ``output`` as in DeviceMixPipeline."""
+
+    def __init__(self, valid_size, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), output="nchw_fp32", resize=None,
+                 device="cuda"):
+        if output not in ("nchw_fp32", "nhwc_bf16"):
+            raise ValueError(output)
+        super().__init__()
+        self.plan, self.output, self.device = CenterCropPlan(valid_size, resize), output, torch.device(device)
+        self.mean, self.std = torch.tensor(mean, dtype=torch.float32), torch.tensor(std, dtype=torch.float32)
+        self._tables = {}                         # the trivial normalise plan per batch size, on the device
+
+    def __call__(self, images):
+        u8 = self.run_crops(images, [self.plan], self.device)[0]
+        n = u8.shape[0]
+        if n not in self._tables:
+            self._tables[n] = pack_mix_plans(identity_plans(n))[0].to(self.device)
+        if self.mean.device != self.device:
+            self.mean, self.std = self.mean.to(self.device), self.std.to(self.device)
+        return ops.mix_normalize_erase(u8, self._tables[n], self.mean, self.std, None, nhwc_bf16=self.output == "nhwc_bf16")
+
+
+class DeviceMultiCrop(_CropStage):
+    """The crop stage of a multi-crop augmentation (DINOAugment, reference transforms.py:249-279: 2 global crops of 224
+    and 8 local crops of 96 per image, each a RandomResizedCrop(..., BICUBIC)): every source is uploaded once and read by
+    all its crops.  ``plans`` = one RandomResizedCropPlan per crop; ``__call__(images)`` -> one uint8 (N, 3, S, S) device
+    batch per plan.  The draws run image by image, crop by crop.  DINOAugment's flip / ColorJitter / grayscale /
+    GaussianBlur / solarize after the crop are not built."""
+
+    def __init__(self, plans, device="cuda"):
+        super().__init__()
+        self.plans, self.device = list(plans), torch.device(device)
+
+    def __call__(self, images, boxes=None):
+        return self.run_crops(images, self.plans, self.device, boxes)

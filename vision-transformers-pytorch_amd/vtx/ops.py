@@ -1057,6 +1057,44 @@ def randaug(images, table):
     return out
 
 
+def resample_plan_bytes():
+    return _lib.load().vtx_resample_plan_bytes()
+
+
+def resample_max_taps():
+    return _lib.load().vtx_resample_max_taps()
+
+
+def resample_coeffs(length, size, first=0, n=None):
+    """PIL's BICUBIC coefficient tables of one axis (``length`` resampled to ``size``, outputs [first, first + n)) as the
+    device builds them -> (xmin [n], count [n], table [n, max_taps]) int32 device tensors."""
+    n = size - first if n is None else n
+    taps = resample_max_taps()
+    raw = torch.empty((2 + taps) * max(n, 1), dtype=torch.int32, device="cuda")
+    check(_lib.load().vtx_resample_coeffs(length, size, first, n, _p(raw), _stream()), "vtx_resample_coeffs")
+    return raw[:n], raw[n:2 * n], raw[2 * n:].view(taps, n).t().contiguous()
+
+
+def resized_crop(buffer, table, out_hw):
+    """Crop + BICUBIC resize + flip of decoded uint8 RGB sources on the device, bit-exact to PIL's
+    ``img.crop(box).resize(size, BICUBIC)``: ``buffer`` = uint8 device bytes holding the sources (H x W x 3 interleaved),
+    ``table`` = the uint8 device table of M records (one per output image) that vtx.input_pipeline.pack_crop_table
+    builds for the buffer vtx.input_pipeline.pack_sources laid out.
+    -> uint8 (M, 3, S_h, S_w)."""
+    _dev(buffer, table)
+    s_h, s_w = (out_hw, out_hw) if isinstance(out_hw, int) else out_hw
+    if buffer.dtype != torch.uint8 or table.dtype != torch.uint8 or table.numel() % resample_plan_bytes():
+        raise VtxError(f"vtx: resized_crop takes a uint8 source buffer and a uint8 table of {resample_plan_bytes()}-byte records")
+    m = table.numel() // resample_plan_bytes()
+    lib = _lib.load()
+    out = torch.empty((m, 3, s_h, s_w), dtype=torch.uint8, device=buffer.device)
+    nws = lib.vtx_resample_workspace_bytes(m, s_h, s_w)
+    ws = torch.empty(max(nws // 4, 1), dtype=torch.int32, device=buffer.device)
+    check(lib.vtx_resized_crop(_p(buffer), buffer.numel(), _p(table), _p(ws), nws, _p(out), m, s_h, s_w, _stream()),
+          "vtx_resized_crop")
+    return out
+
+
 def mix_loss(logits, label1, label2, ratio, eps, reduction="mean"):
     """MixLoss value and its gradient w.r.t. the logits, one kernel.  reduction 'mean': (scalar, d mean / d logits);
     'sum' (the reference treats every other string as sum, loss.py:77-84): (scalar, d sum / d logits); 'none':
