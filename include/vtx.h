@@ -566,6 +566,25 @@ int vtx_resample_coeffs(int L, int S, int first, int n, void* table, void* strea
 int vtx_resized_crop(const void* buf, size_t buf_bytes, const void* table, void* ws, size_t ws_bytes, void* out, int M, int S_h,
                      int S_w, void* stream);
 
+/* ---- DINOAugment after the crop, on the device (csrc/dinoaug.hip; reference
+ * transforms.py:225-294): RandomApply(ColorJitter) -> RandomGrayscale -> GaussianBlur -> Solarize per crop, one launch,
+ * bit-exact to the PIL operations behind them (ImageEnhance, convert("HSV") / convert("RGB"), convert("L"),
+ * ImageFilter.GaussianBlur, ImageOps.solarize).  All random draws are made on the host
+ * (vtx.input_pipeline.DinoAugmentPlan); plan = device array of M records
+ *   {int nops (0..4 jitter ops, applied in order); int code[4] (1 brightness | 2 contrast | 3 saturation | 4 hue);
+ *    float f[4] (the enhance factor of codes 1..3, >= 0); int shift[4] (code 4: the integer added to the H plane, modulo 256);
+ *    int gray (convert("L") x 3); int blur_r, blur_ww, blur_fw (ImagingBoxBlur's integer radius and 24-bit weights of one
+ *    box pass, computed on the host from the Gaussian radius with PIL's float steps; blur_ww == 0: no blur);
+ *    int solarize (threshold 0..256, -1: none)}
+ *   (vtx_dinoaug_plan_bytes() = 72 bytes each; blur_r <= vtx_dinoaug_max_box_radius() = 7).
+ * x: [M, 3, H, W] uint8 (what vtx_resized_crop writes); out: [M, 3, H, W] uint8, distinct from x (what
+ * vtx_mix_normalize_erase then reads); scratch: vtx_dinoaug_scratch_bytes(M, H, W) device bytes -- 0 (scratch may be NULL)
+ * while the blur's two planes fit in LDS (2 * H * W <= 144 KB: every crop up to 271 x 271), the batch's size beyond. */
+size_t vtx_dinoaug_plan_bytes(void);
+int vtx_dinoaug_max_box_radius(void);
+size_t vtx_dinoaug_scratch_bytes(int M, int H, int W);
+int vtx_dinoaug_apply(const void* x, const void* plan, void* scratch, void* out, int M, int C, int H, int W, void* stream);
+
 /* ---- Fused optimizer tail (csrc/optim.hip): nn.utils.clip_grad_norm_ + torch.optim.AdamW.step of the reference's
  * train step (train.py:285-299) as two multi-tensor passes.  Tensors are given as HOST arrays of n device pointers
  * (fp32, any 4-byte alignment) and element counts; the addresses travel in kernel arguments (64 tensors per launch).

@@ -20,6 +20,7 @@
 // other (out / scratch, ping-pong, the last stage lands in out), with a workgroup barrier between stages.  Input and
 // output are uint8 NCHW; x is only read (the partner of stage 0 reads it too).
 #include "vtx_common.h"
+#include "randaug_ops.h"
 
 #define RA_MAX_OPS 8
 #define RA_THREADS 1024
@@ -42,41 +43,6 @@ struct RaPlan {             // one per image, 48 + 32 * RA_MAX_OPS = 304 bytes
   int fill[4];              // fill colour of the affine ops and Cutout (R, G, B, unused)
   RaOp op[RA_MAX_OPS];
 };
-
-// ImagingBlend: out = in1 + alpha * (in2 - in1) in fp32, truncated, clipped (the clip only bites for alpha outside [0, 1]).
-// Separately rounded product and sum: under -ffp-contract=fast hipcc fuses them into an FMA (a contract pragma, __fmul_rn
-// and __fadd_rn do not stop it), which changes the truncated result for some (a, b, alpha); the empty asm hides the
-// product from the combiner.
-__device__ __forceinline__ int ra_blend(int a, int b, float alpha) {
-  float prod = alpha * (float)(b - a);
-  asm volatile("" : "+v"(prod));
-  const float t = (float)a + prod;
-  return t <= 0.f ? 0 : (t >= 255.f ? 255 : (int)t);
-}
-
-// ITU-R 601-2 luma of PIL's RGB -> L conversion (rgb2l: fixed-point weights, rounded)
-__device__ __forceinline__ int ra_luma(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }
-
-// V consecutive bytes (V in {1, 4}; the caller guarantees alignment for V == 4)
-template <int V> struct RaVec { uint8_t v[V]; };
-template <int V> __device__ __forceinline__ RaVec<V> ra_ld(const uint8_t* p) {
-  RaVec<V> r;
-  if constexpr (V == 4) {
-    const uint32_t w = *reinterpret_cast<const uint32_t*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r.v[i] = (uint8_t)(w >> (8 * i));
-  } else {
-    r.v[0] = *p;
-  }
-  return r;
-}
-template <int V> __device__ __forceinline__ void ra_st(uint8_t* p, const RaVec<V>& r) {
-  if constexpr (V == 4) {
-    *reinterpret_cast<uint32_t*>(p) = (uint32_t)r.v[0] | ((uint32_t)r.v[1] << 8) | ((uint32_t)r.v[2] << 16) | ((uint32_t)r.v[3] << 24);
-  } else {
-    *p = r.v[0];
-  }
-}
 
 // out[c][y][x .. x + V) = f(c, y, x + i, i) for every V-pixel group of the image (V divides W)
 template <int V, typename F>
@@ -217,7 +183,7 @@ __global__ __launch_bounds__(RA_THREADS) void randaug_kernel(const uint8_t* __re
             int r;
             if (code == RA_INVERT) r = 255 - u;
             else if (code == RA_POSTERIZE) r = u & p0;
-            else if (code == RA_SOLARIZE) r = u < p0 ? u : 255 - u;
+            else if (code == RA_SOLARIZE) r = ra_solarize(u, p0);
             else r = u < p1 ? min(255, max(0, u + p0)) : u;
             o[c].v[i] = (uint8_t)r;
           }
@@ -232,7 +198,7 @@ __global__ __launch_bounds__(RA_THREADS) void randaug_kernel(const uint8_t* __re
         for (int e = tid; e < HW; e += RA_THREADS) part += (unsigned)ra_luma(src[e], src[HW + e], src[2 * HW + e]);
         atomicAdd(&lsum, (unsigned long long)part);
         __syncthreads();
-        mean = (int)((double)lsum / (double)HW + 0.5);
+        mean = ra_contrast_mean(lsum, HW);
       }
       ra_pass<V>(dst, H, W, [&](int y, int x0, int p, RaVec<V>* o) {
         RaVec<V> v[3];

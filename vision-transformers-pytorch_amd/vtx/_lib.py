@@ -208,6 +208,10 @@ _SIGNATURES = {
     "vtx_resample_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "vtx_resample_coeffs": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vtx_resized_crop": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "vtx_dinoaug_plan_bytes": (c_size_t, []),
+    "vtx_dinoaug_max_box_radius": (c_int, []),
+    "vtx_dinoaug_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "vtx_dinoaug_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "vtx_ema_update": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p]),
     "vtx_dino_loss_workspace": (c_size_t, [c_int, c_int]),
     "vtx_dino_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int,

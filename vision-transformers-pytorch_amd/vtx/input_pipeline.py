@@ -19,6 +19,10 @@ any size): RandomResizedCrop(size, BICUBIC) + RandomHorizontalFlip (factory.py:1
 (csrc/resample.hip, bit-exact to PIL's ``crop`` + ``resize``), fed by one asynchronous upload of the crops' pixels.
 ``DeviceEvalPipeline`` is the validation transform (Resize + CenterCrop + ToTensor + Normalize, factory.py:215-222) and
 ``DeviceMultiCrop`` the crop stage of DINOAugment (transforms.py:249-279) on the same kernel.
+
+``DeviceDinoAugment`` is the whole of DINOAugment (transforms.py:216-294) from decoded images: the ten crops, then per crop
+ColorJitter / RandomGrayscale / GaussianBlur / Solarize in one launch per crop size (csrc/dinoaug.hip, bit-exact to the PIL
+operations behind them; the draws are ``DinoAugmentPlan``'s), then ToTensor + Normalize.
 """
 import math
 import random as _random
@@ -506,6 +510,16 @@ class _CropStage(_UploadRing):
         """The crop stage shared by the pipelines: ``plans`` = one plan per crop of every image (all images get the same
         list); ``boxes[k][j]`` = the explicit box of image k, crop j (None: drawn, image by image, crop by crop).
         -> list of uint8 (N, 3, S_h, S_w) device tensors, one per plan; one upload, one launch per distinct output size."""
+        out = [None] * len(plans)
+        for js, res in self.run_crops_by_size(images, plans, dev, boxes):
+            n = res.shape[0] // len(js)
+            for i, j in enumerate(js):
+                out[j] = res[i * n:(i + 1) * n]
+        return out
+
+    def run_crops_by_size(self, images, plans, dev, boxes=None):
+        """``run_crops`` before the split into plans: -> [(js, uint8 (len(js) * N, 3, S_h, S_w))], one entry per distinct
+        output size; ``js`` = the indices of the plans of that size, whose batches follow each other in the tensor."""
         images = _as_images(images)
         records = []
         for k, im in enumerate(images):
@@ -515,14 +529,12 @@ class _CropStage(_UploadRing):
                 records.append(rec)
         buf, placed = self.upload_crops(images, records, dev)
         self.crop_records = records
-        out = [None] * len(plans)
+        out = []
         for hw in sorted({p.out_hw for p in plans}):
             js = [j for j, p in enumerate(plans) if p.out_hw == hw]
             recs = [r for j in js for r in records if r["plan"] == j]          # plan-major: each plan's batch is contiguous
             table = self.upload(pack_crop_table(recs, placed), dev, "crops")
-            res = ops.resized_crop(buf, table, hw)
-            for i, j in enumerate(js):
-                out[j] = res[i * len(images):(i + 1) * len(images)]
+            out.append((js, ops.resized_crop(buf, table, hw)))
         return out
 
 
@@ -632,7 +644,7 @@ class DeviceMultiCrop(_CropStage):
     and 8 local crops of 96 per image, each a RandomResizedCrop(..., BICUBIC)): every source is uploaded once and read by
     all its crops.  ``plans`` = one RandomResizedCropPlan per crop; ``__call__(images)`` -> one uint8 (N, 3, S, S) device
     batch per plan.  The draws run image by image, crop by crop.  DINOAugment's flip / ColorJitter / grayscale /
-    GaussianBlur / solarize after the crop are not built."""
+    GaussianBlur / solarize after the crop are ``DeviceDinoAugment``'s."""
 
     def __init__(self, plans, device="cuda"):
         super().__init__()
@@ -640,3 +652,181 @@ class DeviceMultiCrop(_CropStage):
 
     def __call__(self, images, boxes=None):
         return self.run_crops(images, self.plans, self.device, boxes)
+
+
+MAX_BOX_RADIUS = 7                                # = vtx_dinoaug_max_box_radius(): GaussianBlur radii up to ~7.9
+
+
+def _f32(v):
+    """The C float nearest to v.  A float +, -, *, / is done below as the double operation rounded by this: for float
+    operands that is the correctly rounded float result (53 >= 2 * 24 + 2 bits)."""
+    return struct.unpack("<f", struct.pack("<f", v))[0]
+
+
+def blur_box_params(radius):
+    """ImageFilter.GaussianBlur(radius) -> (R, ww, fw) of one of PIL's box passes (BoxBlur.c: _gaussian_blur_radius with 3
+    passes in C floats around a double sqrt / floor, then ImagingBoxBlur's integer radius and 24-bit weights):
+    out[i] = (ww * sum_{|d| <= R} x[i + d] + fw * (x[i - R - 1] + x[i + R + 1]) + 2^23) >> 24."""
+    r = _f32(radius)
+    sigma2 = _f32(_f32(r * r) / 3.0)
+    box = _f32(math.sqrt(12.0 * sigma2 + 1.0))
+    l = _f32(math.floor((box - 1.0) / 2.0))
+    a = _f32(_f32(2.0 * l + 1.0) * _f32(_f32(l * _f32(l + 1.0)) - _f32(3.0 * sigma2)))
+    a = _f32(a / _f32(6.0 * _f32(sigma2 - _f32(_f32(l + 1.0) * _f32(l + 1.0)))))
+    fr = _f32(l + a)
+    R = int(fr)
+    ww = int(_f32(float(1 << 24) / _f32(_f32(fr * 2.0) + 1.0)))           # UINT32 / float: a C float division
+    return R, ww, ((1 << 24) - (2 * R + 1) * ww) // 2
+
+
+class DinoAugmentPlan:
+    """Host side of reference transforms.DINOAugment (transforms.py:216-294) with its constructor arguments: the ten crops
+    (``crops``: one RandomResizedCropPlan each, flip_p 0.5) and, per crop, RandomApply([ColorJitter(0.4, 0.4, 0.2, 0.1)],
+    0.8), RandomGrayscale(0.2), GaussianBlur(0.1, 2, p = 1.0 / 0.1 / 0.5 for global 1 / global 2 / local) and, for global 2,
+    Solarize(128, 0.2).
+
+    ``draw`` makes the random calls in the reference's order, image by image, crop by crop; per crop, on ``generator`` (a
+    torch CPU generator, None = torch's global one): the box attempts and the flip (RandomResizedCropPlan.draw), then
+    ``torch.rand(1)`` (jitter skipped when 0.8 < it), and only when applied ``torch.randperm(4)`` (the order of 0
+    brightness, 1 contrast, 2 saturation, 3 hue) and ``torch.empty(1).uniform_`` for brightness [0.6, 1.4], contrast
+    [0.6, 1.4], saturation [0.8, 1.2], hue [-0.1, 0.1]; then ``torch.rand(1) < 0.2`` for grayscale.  On ``rng`` (a
+    ``random.Random``, None = the module, which is what the reference's RandomTransform consumes): ``uniform(0.1, 2)`` for
+    the blur radius ALWAYS (sample() runs before the probability check), ``random()`` unless p == 1.0; for global 2 one
+    more ``random()`` for the solarize.  That is torchvision >= 0.9's sequence as read from its source; torchvision is not
+    installed where this was written, so it was NOT checked against it -- every draw can be given explicitly instead.
+
+    A crop's parameters: dict(box=(top, left, h, w, flip), jitter=(order, (b, c, s, hue factor)) or None, gray=bool,
+    blur=radius or None, solarize=bool).  Hue: the H plane gets ``int(hue_factor * 255)`` added -- truncation toward zero,
+    then modulo 256 -- which is how torchvision's ``np.uint8(hue_factor * 255)`` wrapping add is read here (an assumption).
+    """
+
+    JITTER_P, GRAY_P, SOLARIZE_P, SOLARIZE_THRESHOLD = 0.8, 0.2, 0.2, 128
+    RANGES = ((0.6, 1.4), (0.6, 1.4), (0.8, 1.2), (-0.1, 0.1))     # brightness, contrast, saturation, hue
+    BLUR_RADIUS = (0.1, 2)
+
+    def __init__(self, global_crop_size, local_crop_size, global_crop_scale, local_crop_scale, n_local_crop, generator=None,
+                 rng=None):
+        self.generator, self.rng = generator, rng or _random
+        mk = lambda size, scale: RandomResizedCropPlan(size, scale=scale, flip_p=0.5, generator=generator)
+        self.crops = [mk(global_crop_size, global_crop_scale), mk(global_crop_size, global_crop_scale)]
+        self.crops += [mk(local_crop_size, local_crop_scale) for _ in range(n_local_crop)]
+        self.blur_p = [1.0, 0.1] + [0.5] * n_local_crop
+        self.solarize_p = [None, self.SOLARIZE_P] + [None] * n_local_crop
+
+    def draw_augment(self, j):
+        """The draws of crop j after its box and flip -> dict(jitter, gray, blur, solarize)."""
+        g = self.generator
+        jitter = None
+        if not self.JITTER_P < torch.rand(1, generator=g).item():
+            order = tuple(torch.randperm(4, generator=g).tolist())
+            jitter = (order, tuple(torch.empty(1).uniform_(lo, hi, generator=g).item() for lo, hi in self.RANGES))
+        gray = bool(torch.rand(1, generator=g).item() < self.GRAY_P)
+        radius = self.rng.uniform(*self.BLUR_RADIUS)
+        p = self.blur_p[j]
+        blur = radius if p == 1.0 or self.rng.random() < p else None
+        solarize = self.solarize_p[j] is not None and self.rng.random() < self.solarize_p[j]
+        return dict(jitter=jitter, gray=gray, blur=blur, solarize=solarize)
+
+    def draw(self, shapes):
+        """shapes = [(h, w)] of the decoded images -> params[k][j] of image k, crop j."""
+        out = []
+        for h, w in shapes:
+            row = []
+            for j, crop in enumerate(self.crops):
+                box = crop.draw(h, w)
+                row.append(dict(self.draw_augment(j), box=box))
+            out.append(row)
+        return out
+
+    def encode(self, p):
+        """A crop's parameters -> its record of the device table (csrc/dinoaug.hip DaPlan); raises VtxError for anything
+        the kernel does not compute exactly."""
+        code, f, shift = [0] * 4, [0.0] * 4, [0] * 4
+        nops = 0
+        if p.get("jitter") is not None:
+            order, values = p["jitter"]
+            if sorted(order) != sorted(set(order)) or not all(o in (0, 1, 2, 3) for o in order) or len(values) != 4:
+                raise ops.VtxError(f"vtx: ColorJitter order {order!r}: distinct ops out of 0..3, and four values")
+            for o in order:
+                code[nops] = o + 1
+                if o == 3:
+                    if not -0.5 <= values[3] <= 0.5:
+                        raise ops.VtxError(f"vtx: hue factor {values[3]} outside [-0.5, 0.5]")
+                    shift[nops] = int(values[3] * 255)
+                else:
+                    if not values[o] >= 0:
+                        raise ops.VtxError(f"vtx: negative {('brightness', 'contrast', 'saturation')[o]} factor {values[o]}")
+                    f[nops] = float(values[o])
+                nops += 1
+        R = ww = fw = 0
+        if p.get("blur") is not None:
+            if not p["blur"] >= 0:
+                raise ops.VtxError(f"vtx: GaussianBlur radius {p['blur']}")
+            R, ww, fw = blur_box_params(p["blur"])
+            if R > MAX_BOX_RADIUS:
+                raise ops.VtxError(f"vtx: GaussianBlur radius {p['blur']} needs box radius {R} > {MAX_BOX_RADIUS}: not built")
+        sol = self.SOLARIZE_THRESHOLD if p.get("solarize") else -1
+        return struct.pack("<i4i4f4ii3ii", nops, *code, *f, *shift, int(bool(p.get("gray"))), R, ww, fw, sol)
+
+    def pack(self, params):
+        """params: the crops' parameter dicts in the batch's order -> uint8 [len(params) * vtx_dinoaug_plan_bytes()]"""
+        return torch.frombuffer(bytearray(b"".join(self.encode(p) for p in params)), dtype=torch.uint8)
+
+
+class DeviceDinoAugment(_CropStage):
+    """reference transforms.DINOAugment (transforms.py:216-294) from decoded images, on the device: list of N decoded
+    H x W x 3 uint8 host images -> list of 2 + n_local_crop normalised batches (N, 3, S, S), global crops first -- the list
+    ``vtx.dino.dino_train_step`` takes.  One upload of the pixels the crops read, then per crop size three launches: crop +
+    BICUBIC resize + flip (csrc/resample.hip), ColorJitter / grayscale / GaussianBlur / solarize (csrc/dinoaug.hip), ToTensor
+    + Normalize (csrc/input.hip, the trivial plan); the uint8 stages are bit-exact to PIL.  ``output`` as in
+    DeviceMixPipeline.  ``generator`` / ``rng`` (or ``seed`` for a fresh ``random.Random``): see DinoAugmentPlan.
+
+    ``__call__(images, params=None)``: ``params[k][j]`` = the parameter dict of image k, crop j (DinoAugmentPlan's layout,
+    ``box`` included) replaces every draw.  ``augment_params`` and ``crop_records`` keep what the last call used."""
+
+    def __init__(self, global_crop_size, local_crop_size, global_crop_scale, local_crop_scale, n_local_crop,
+                 mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), output="nchw_fp32", generator=None, rng=None, seed=None,
+                 device="cuda"):
+        if output not in ("nchw_fp32", "nhwc_bf16"):
+            raise ValueError(output)
+        super().__init__()
+        if rng is None and seed is not None:
+            rng = _random.Random(seed)
+        self.plan = DinoAugmentPlan(global_crop_size, local_crop_size, global_crop_scale, local_crop_scale, n_local_crop,
+                                    generator, rng)
+        self.output, self.device = output, torch.device(device)
+        self.mean, self.std = torch.tensor(mean, dtype=torch.float32), torch.tensor(std, dtype=torch.float32)
+        self.augment_params = []
+        self._tables = {}                         # the trivial normalise plan per batch size, on the device
+
+    def augment_u8(self, images, params=None):
+        """The uint8 stages: -> [(js, uint8 (len(js) * N, 3, S, S))] per crop size (run_crops_by_size's layout)."""
+        images = _as_images(images)
+        crops = self.plan.crops
+        if params is None:
+            params = self.plan.draw([im.shape[:2] for im in images])
+        elif len(params) != len(images) or any(len(row) != len(crops) for row in params):
+            raise ops.VtxError(f"vtx: params must hold {len(crops)} crops for each of the {len(images)} images")
+        sizes = sorted({p.out_hw for p in crops})
+        tables = []
+        for hw in sizes:                          # plan-major like the crop records; raises before anything is launched
+            js = [j for j, p in enumerate(crops) if p.out_hw == hw]
+            tables.append(self.plan.pack([params[k][j] for j in js for k in range(len(images))]))
+        self.augment_params = params
+        by_size = self.run_crops_by_size(images, crops, self.device, [[p["box"] for p in row] for row in params])
+        return [(js, ops.dinoaug(u8, self.upload(t, self.device, f"dinoaug{i}")))
+                for i, ((js, u8), t) in enumerate(zip(by_size, tables))]
+
+    def __call__(self, images, params=None):
+        if self.mean.device != self.device:
+            self.mean, self.std = self.mean.to(self.device), self.std.to(self.device)
+        out = [None] * len(self.plan.crops)
+        for js, u8 in self.augment_u8(images, params):
+            m = u8.shape[0]
+            if m not in self._tables:
+                self._tables[m] = pack_mix_plans(identity_plans(m))[0].to(self.device)
+            x = ops.mix_normalize_erase(u8, self._tables[m], self.mean, self.std, None, nhwc_bf16=self.output == "nhwc_bf16")
+            n = m // len(js)
+            for i, j in enumerate(js):
+                out[j] = x[i * n:(i + 1) * n]
+        return out

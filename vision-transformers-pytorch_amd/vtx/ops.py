@@ -1095,6 +1095,33 @@ def resized_crop(buffer, table, out_hw):
     return out
 
 
+def dinoaug_plan_bytes():
+    return _lib.load().vtx_dinoaug_plan_bytes()
+
+
+def dinoaug_max_box_radius():
+    return _lib.load().vtx_dinoaug_max_box_radius()
+
+
+def dinoaug(images, table):
+    """DINOAugment after the crop (ColorJitter / grayscale / GaussianBlur / solarize) of a uint8 RGB batch (M, 3, H, W) on
+    the device, one launch, bit-exact to PIL: ``table`` = the uint8 device table of M records that
+    vtx.input_pipeline.DinoAugmentPlan.pack builds.  -> uint8 (M, 3, H, W)."""
+    _dev(images, table)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[1] != 3:
+        raise VtxError(f"vtx: dinoaug takes uint8 (M, 3, H, W) images, got {images.dtype} {tuple(images.shape)}")
+    x = images if images.is_contiguous() else images.contiguous()
+    m, c, h, w = x.shape
+    if table.dtype != torch.uint8 or table.numel() != m * dinoaug_plan_bytes():
+        raise VtxError(f"vtx: dinoaug table must be {m} x {dinoaug_plan_bytes()} uint8 bytes")
+    lib = _lib.load()
+    out = torch.empty_like(x)
+    nscr = lib.vtx_dinoaug_scratch_bytes(m, h, w)
+    scratch = torch.empty(nscr, dtype=torch.uint8, device=x.device) if nscr else None
+    check(lib.vtx_dinoaug_apply(_p(x), _p(table), _p(scratch), _p(out), m, c, h, w, _stream()), "vtx_dinoaug_apply")
+    return out
+
+
 def mix_loss(logits, label1, label2, ratio, eps, reduction="mean"):
     """MixLoss value and its gradient w.r.t. the logits, one kernel.  reduction 'mean': (scalar, d mean / d logits);
     'sum' (the reference treats every other string as sum, loss.py:77-84): (scalar, d sum / d logits); 'none':
