@@ -620,6 +620,36 @@ int vtx_dino_loss(const void* student, const void* teacher, const float* center,
 int vtx_mix_loss(const void* logits, const int64_t* label1, const int64_t* label2, const float* ratio, void* dlogits,
                  float* loss_rows, int B, int K, float eps, float gscale, int dtype, void* stream);
 
+/* ---- Loss and prec@k meters (csrc/metrics.hip; reference train.py:277-281, 335-386, train_util.py:34-67): per-row
+ * cross entropy and the label's rank in one sweep of the (B, K) logits, then -- in the same call, on the same stream --
+ * the batch added to a device meter.  No host synchronisation; the caller reads the meter when it wants the numbers.
+ *   logits [B, K] (dtype; any row alignment, any K >= 1), labels [B] int64;
+ *   ce_rows [B] fp32 = logsumexp(row) - row[label]  (F.cross_entropy, reduction "none");
+ *   rank [B] int32   = #{j : x_j > x_l} + #{j < l : x_j == x_l}: the label's position in a STABLE descending sort --
+ *                      among equal logits the lower class index ranks first.  The label is in the top k exactly when
+ *                      rank < k.  (torch.topk leaves the order of ties unspecified; this rule is the contract.)
+ *   meter [2 + nk] fp64 or NULL (rows only): [n, loss_sum, hits_ks0, hits_ks1, ...]; the call ADDS the batch's counted
+ *                      rows, their cross-entropy sum and their rows with rank < ks[i].  One workgroup, fixed summation
+ *                      order, no atomics: the same inputs give the same bits.  ks: HOST array of nk (0..8) values >= 1,
+ *                      passed to the kernel by value.
+ *   loss_override     NULL, or one fp32 DEVICE scalar (a batch-mean loss): loss_sum += *loss_override * loss_scale *
+ *                      (counted rows) replaces the cross-entropy sum -- how the training loop meters MixLoss
+ *                      (losses.update(loss.item() * grad_accum, batch), train.py:279).
+ * Edge rules:
+ *   - NaN logits order above +inf (as torch.topk does) and tie with each other by class index; the cross entropy of a
+ *     row that holds one is NaN.
+ *   - -inf logits (masked classes) are allowed when the row has at least one finite logit: they add nothing to the
+ *     sum of exponentials.
+ *   - label == ignore_index (nn.CrossEntropyLoss's default is -100): ce_rows = 0, rank = -1, the row is NOT counted.
+ *   - any other label outside [0, K) is never used as an index: ce_rows = NaN, rank = K, the row IS counted -- the
+ *     poison shows in the epoch's loss.
+ *   - ks[i] > K: every counted row is a hit (rank <= K < ks[i]).
+ * Errors: VTX_ERR_NULL (logits / labels / ce_rows / rank, or ks with nk > 0), VTX_ERR_SHAPE (B, K < 1; nk outside 0..8;
+ * ks[i] < 1), VTX_ERR_DTYPE, VTX_ERR_ALIGN (logits not aligned to its element size). */
+int vtx_cls_metrics(const void* logits, const int64_t* labels, float* ce_rows, int32_t* rank, double* meter,
+                    const int32_t* ks, int nk, const float* loss_override, float loss_scale, int B, int K,
+                    int64_t ignore_index, int dtype, void* stream);
+
 /* ---- Multi-tensor weight cast (csrc/cast.hip): all fp32 Linear / Conv weights of a model -> bf16, plain [out][in]
  * and transposed [in][out], in one launch per forward.  This is the per-call weight cast of the reference's bf16
  * autocast (torch.cuda.amp.autocast around model(input), train.py:273-274) done once for the whole model.

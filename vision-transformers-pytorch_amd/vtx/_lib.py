@@ -218,6 +218,8 @@ _SIGNATURES = {
                               c_int, c_int, c_float, c_float, c_float, c_int, c_void_p]),
     "vtx_mix_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float,
                              c_int, c_void_p]),
+    "vtx_cls_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float, c_int,
+                                c_int, c_int64, c_int, c_void_p]),
     "vtx_cast_desc_bytes": (c_size_t, []),
     "vtx_cast_weights": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vtx_patch_gather": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -1142,6 +1142,33 @@ def mix_loss(logits, label1, label2, ratio, eps, reduction="mean"):
     return (rows.sum() / B if reduction == "mean" else rows.sum()), dl
 
 
+def cls_metrics(logits, labels, meter=None, ks=(), loss=None, loss_scale=1.0, ignore_index=-100):
+    """Per-row cross entropy and rank of the label (stable descending order: rank < k <=> the label is in the top k) of
+    (B, K) float32 / bfloat16 logits, one kernel; with ``meter`` (a float64 device tensor of 2 + len(ks) values
+    [n, loss_sum, hits...]) a second launch in the same call adds the batch to it.  ``loss``: a one-element float32
+    device tensor whose value * loss_scale * (counted rows) goes to loss_sum instead of the cross-entropy sum.  ``ks``:
+    a sequence of ints or a prepared ``ctypes.c_int32`` array.  No host synchronisation.  -> (ce_rows fp32 [B], rank
+    int32 [B]); edge rules: include/vtx.h."""
+    _dev(logits, labels, meter, loss)
+    if logits.dim() != 2 or labels.dim() != 1 or labels.numel() != logits.shape[0]:
+        raise VtxError(f"vtx: cls_metrics takes (B, K) logits and (B,) labels, got {tuple(logits.shape)} / {tuple(labels.shape)}")
+    B, K = logits.shape
+    l = labels if labels.dtype == torch.int64 else labels.to(torch.int64)
+    nk = len(ks)
+    kk = ks if isinstance(ks, ctypes.Array) else (ctypes.c_int32 * nk)(*[int(k) for k in ks])
+    if meter is not None and (meter.dtype != torch.float64 or meter.numel() != 2 + nk):
+        raise VtxError(f"vtx: the meter is a float64 tensor of 2 + {nk} values")
+    if loss is not None and (loss.dtype != torch.float32 or loss.numel() != 1):
+        raise VtxError("vtx: cls_metrics loss= is ONE float32 device value (a batch-mean loss)")
+    ce = torch.empty(B, dtype=torch.float32, device=logits.device)
+    rank = torch.empty(B, dtype=torch.int32, device=logits.device)
+    with _timed("cls_metrics_kernel", 0.0, float(B) * K * logits.element_size() + 16.0 * B):
+        check(_lib.load().vtx_cls_metrics(_p(logits), _p(l), _p(ce), _p(rank), _p(meter), kk if nk else None, nk, _p(loss),
+                                          float(loss_scale), B, K, int(ignore_index), _dt(logits), _stream()),
+              "vtx_cls_metrics")
+    return ce, rank
+
+
 def l2norm_fwd(x, eps=1e-12):
     """y = x / max(||x||_2, eps) over the last dim; returns (y, row norms)."""
     _dev(x)

@@ -118,7 +118,7 @@ def backward_ddp(loss, ddp, boundary, ddp_sync, fresh):
 
 
 def train_step(model, criterion, optimizer, batch, clip_grad_norm=5.0, autocast_dtype=torch.bfloat16,
-               grad_accum=1, ddp=None, micro_step=None, ddp_sync="boundary", loader_len=None):
+               grad_accum=1, ddp=None, micro_step=None, ddp_sync="boundary", loader_len=None, meter=None):
     """One micro-batch of the reference's loop body (train.py:273-299).  ``batch`` = (input NCHW fp32, label1, label2,
     ratio) on the device.  Like the reference, clip + optimizer step + zero_grad run only on accumulation boundaries:
     ``(micro_step + 1) % grad_accum == 0`` (``micro_step`` = the loader index ``i``, required when grad_accum > 1) or, with
@@ -128,12 +128,18 @@ def train_step(model, criterion, optimizer, batch, clip_grad_norm=5.0, autocast_
 
     ``ddp`` (vtx.ddp.GradAllReduce) overlaps the gradient all-reduce with backward; its ``finish()`` is the
     only synchronisation point before clipping (``ddp_sync``: see backward_ddp).  Returns the (unsynchronised) loss tensor.
+
+    ``meter`` (vtx.metrics.DeviceMeter): the reference's log numbers of this micro-batch (train.py:277-281: prec@1 / prec@5
+    of ``out`` against label1, and ``loss * grad_accum``) go to the device meter in one C call after the forward -- no
+    ``.item()``, the host keeps running ahead.  None (default): the step is exactly what it is without this argument.
     """
     x, l1, l2, ratio = batch
     boundary = accumulation_boundary(grad_accum, micro_step, loader_len)
     with torch.autocast("cuda", dtype=autocast_dtype, enabled=autocast_dtype is not None):
         out = model(x)
         loss = criterion(out, l1, l2, ratio) / grad_accum
+    if meter is not None:
+        meter.update(out.detach(), l1, loss=loss.detach(), loss_scale=grad_accum)
     # Side-stream weight gradients (functional.deferred_wgrad) need "one gradient per parameter, .grad None on entry":
     # true for the first micro-batch after zero_grad(set_to_none) of these single-pass models, not while accumulating.
     fresh = grad_accum == 1 or micro_step % grad_accum == 0
