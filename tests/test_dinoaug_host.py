@@ -258,7 +258,7 @@ def test_abi_header_binding_and_library_agree():
     lib = _lib.load()
     for n in names:
         assert n in declared and n in _lib.exported_symbols() and hasattr(lib, n), n
-    assert lib.vtx_abi_version() == _lib.ABI_VERSION == 29
+    assert lib.vtx_abi_version() == _lib.ABI_VERSION == 30
     assert ops.dinoaug_plan_bytes() == 72
     assert lib.vtx_dinoaug_scratch_bytes(128, 224, 224) == 0 and lib.vtx_dinoaug_scratch_bytes(512, 96, 96) == 0
     assert lib.vtx_dinoaug_scratch_bytes(4, 300, 300) == 4 * 3 * 300 * 300 and lib.vtx_dinoaug_scratch_bytes(0, 300, 300) == 0

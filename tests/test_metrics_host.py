@@ -1,5 +1,6 @@
 """Host-side checks of the loss / prec@k meters (no GPU): the C entry is declared and bound, the Python surface refuses
-what it cannot run, and the ABI version did not move (the change adds one symbol and alters none)."""
+what it cannot run, and the ABI version of the library and of the binding agree (the entry itself added one symbol and
+altered none; the number has moved since with vtx_l2norm_bwd's signature)."""
 import os
 import re
 
@@ -22,9 +23,9 @@ def test_cls_metrics_is_declared_bound_and_exported():
         assert rule in header, f"include/vtx.h does not state the rule: {rule}"
 
 
-def test_abi_version_is_unchanged():
+def test_abi_version():
     from vtx import _lib
-    assert _lib.load().vtx_abi_version() == 29 == _lib.ABI_VERSION
+    assert _lib.load().vtx_abi_version() == 30 == _lib.ABI_VERSION
 
 
 def test_entry_refuses_bad_arguments_before_any_launch():

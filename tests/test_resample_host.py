@@ -269,7 +269,7 @@ def test_abi_header_binding_and_library_agree():
     lib = _lib.load()
     for n in names:
         assert n in declared and n in _lib.exported_symbols() and hasattr(lib, n), n
-    assert lib.vtx_abi_version() == _lib.ABI_VERSION == 29
+    assert lib.vtx_abi_version() == _lib.ABI_VERSION == 30
     assert ops.resample_plan_bytes() == 64 and ops.resample_max_taps() == MAX_TAPS == 65
     assert lib.vtx_resample_workspace_bytes(128, 224, 224) == 128 * (2 + 65) * 448 * 4
     assert lib.vtx_resample_workspace_bytes(0, 224, 224) == 0

@@ -646,13 +646,14 @@ class L2NormFn(Function):
     def forward(ctx, x, eps):
         y, nrm = ops.l2norm_fwd(_c(x), eps)
         ctx.save_for_backward(y, nrm)
+        ctx.eps = eps
         return y
 
     @staticmethod
     def backward(ctx, dy):
         side_fence(dy.device)
         y, nrm = ctx.saved_tensors
-        return ops.l2norm_bwd(_c(dy), y, nrm), None
+        return ops.l2norm_bwd(_c(dy), y, nrm, ctx.eps), None
 
 
 class AttentionMeta:

@@ -1170,7 +1170,7 @@ def cls_metrics(logits, labels, meter=None, ks=(), loss=None, loss_scale=1.0, ig
 
 
 def l2norm_fwd(x, eps=1e-12):
-    """y = x / max(||x||_2, eps) over the last dim; returns (y, row norms)."""
+    """y = x / max(||x||_2, eps) over the last dim; returns (y, the unclamped row norms ||x||_2)."""
     _dev(x)
     C = x.shape[-1]
     rows = x.numel() // C
@@ -1180,11 +1180,13 @@ def l2norm_fwd(x, eps=1e-12):
     return y, nrm
 
 
-def l2norm_bwd(dy, y, nrm):
+def l2norm_bwd(dy, y, nrm, eps=1e-12):
+    """dx of l2norm_fwd from its outputs (y, nrm) and its ``eps``: rows with nrm < eps sit on the clamp, dx = dy / eps there."""
     _dev(dy, y, nrm)
     C = y.shape[-1]
     dx = torch.empty_like(y)
-    check(_lib.load().vtx_l2norm_bwd(_p(dy), _p(y), _p(nrm), _p(dx), y.numel() // C, C, _dt(y), _stream()), "vtx_l2norm_bwd")
+    check(_lib.load().vtx_l2norm_bwd(_p(dy), _p(y), _p(nrm), _p(dx), y.numel() // C, C, float(eps), _dt(y), _stream()),
+          "vtx_l2norm_bwd")
     return dx
 
 
