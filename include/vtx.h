@@ -231,8 +231,9 @@ int vtx_attention_bwd(const void* qkv, const void* o, const void* dout, const fl
  * so -- the backward regenerates the decision from the same (drop_p, seed), no mask tensor exists in HBM -- and kept
  * probabilities are scaled by 1 / (1 - drop_p).  problem = (image * nW + window) * nH + head.  keep != NULL replaces the hash by
  * an explicit mask [problems][L][L] of bytes (1 = keep): the parity tests pass the mask the reference drew.  0 < drop_p < 1.
- * Global attention of any length (key-block kernels beyond 224 tokens), window attention of <= 64 tokens (head dim 32 | 64) or <= 160
- * tokens (head dim 32).
+ * Global attention of any length (key-block kernels beyond 224 tokens); with a window, a bias or a mask the register-resident kernels:
+ * <= 160 tokens (head dim 32) or <= 224 tokens (head dim 64), VTX_ERR_SHAPE beyond -- and, with a bias, <= 160 tokens in the backward
+ * (the register-resident bias gradient).
  * vtx_attn_keep_mask writes the hash's decisions [nprob][Lq][Lk] (what the kernels regenerate) for tests / an external checker. */
 int vtx_attention_fwd_drop(const void* qkv, void* o, float* lse, const float* bias, const uint8_t* mask, int B, int L,
                            int nH, int D, int swin, int H, int W, int win, int shift, int dtype, float drop_p, uint64_t seed,

@@ -4,8 +4,8 @@ gpu_util.check takes ONE number per tensor (relative L2), which averages a local
 column bias, one sample's DropPath scale.  ``check_elementwise`` asserts |got - ref| <= env at EVERY element instead.  ``env`` is
 never a measured number: each builder below computes it in fp64 from the arithmetic its kernel is documented to do, with
 absolute-value products, and carries its derivation.  tests/test_elementwise_host.py proves every builder on the CPU (a torch
-model of a correct kernel has zero violations; planted defects are found and located); tests/test_gpu_elementwise.py runs the
-kernels against them.
+model of a correct kernel has zero violations; planted defects are found and located); tests/test_gpu_elementwise.py and
+tests/test_gpu_attn_drop_elementwise.py (attention dropout, the generic window path) run the kernels against them.
 
 Conventions, stated once:
   U32 = 2^-24   unit roundoff of an fp32 operation (every accumulator, every epilogue expression)
@@ -312,9 +312,19 @@ class Attn:
     p = exp(s - m): relative 2 d_s (the score's and the running maximum's) + E_EXP; packed to bf16: u_p; the sum over Lk keys and the
     division by l (whose own relative error d_s + E_EXP + Lk U32 is of the same kind): (Lk + 2) U32; store: u |o|.
         env_o   = TWO * ( u |o| + (u_p + 2 d_s + 2 E_EXP + (Lk + 2) U32) sum_k p_k |v_k| )
-        env_lse = d_s + E_EXP + 2^-23 |lse|"""
+        env_lse = d_s + E_EXP + 2^-23 |lse|
 
-    def __init__(self, q, k, v, scale, add=None, bf16=True, out_dtype=torch.bfloat16):
+    Dropout of the probabilities (``keep``: 0 / 1, broadcastable to [P, H, Lq, Lk]; ``drop_p``).  The kernels multiply the
+    UNNORMALISED exponentials by F = keep / (1 - p) after the row sum is taken (attention.hip attn_fwd_kernel, attention_sr.hip;
+    attention_long.hip inside the key-block loop, the running sum stays the undropped one), so lse and p are the undropped softmax
+    and env_lse is unchanged;  o = (p o F) v.  F is the fp32 1.f / (1.f - p) of the fp32 p the ABI receives (the reference takes the
+    same fp32 p): a subtraction and a division form it and ONE fp32 multiply applies it, U_F = 3 U32 relative on every kept cell, and
+    every sum p |v| carries F:
+        env_o   = TWO * ( u |o| + (u_p + 2 d_s + 2 E_EXP + (Lk + 2) U32 + U_F) sum_k p_k F_k |v_k| )
+    A query row whose keys are all dropped (or whose kept keys are all masked: p = 0 there) has p F = 0 in every cell: o = 0 and
+    env_o = 0 EXACTLY, whatever lse is -- the kernel has to store exact zeros there."""
+
+    def __init__(self, q, k, v, scale, add=None, bf16=True, out_dtype=torch.bfloat16, keep=None, drop_p=0.0):
         self.q, self.k, self.v = f64(q), f64(k), f64(v)
         self.scale, self.u_p, self.u = float(scale), (U16 if bf16 else 0.0), u_of(out_dtype)
         self.D, self.Lq, self.Lk = self.q.shape[-1], self.q.shape[-2], self.k.shape[-2]
@@ -323,11 +333,22 @@ class Attn:
             s = s + f64(add)
         self.lse = torch.logsumexp(s, -1)
         self.p = torch.exp(s - self.lse[..., None])
-        self.o = self.p @ self.v
+        self.F = None
+        if keep is not None:
+            p32 = float(torch.tensor(float(drop_p), dtype=torch.float32))           # the fp32 probability the kernels receive
+            assert 0.0 < p32 < 1.0, "dropout probability outside (0, 1)"
+            kp = f64(keep)
+            assert bool(((kp == 0) | (kp == 1)).all()), "keep must hold 0 / 1"
+            self.F = (kp / (1.0 - p32)).expand(self.p.shape)
+        self.pF = self.p if self.F is None else self.p * self.F                       # what multiplies v and dO
+        self.u_F = 0.0 if self.F is None else 3 * U32
+        self.o = self.pF @ self.v
         sabs = self.scale * (self.q.abs() @ self.k.abs().transpose(-1, -2))
         self.d_s = (self.D + 2) * U32 * sabs.amax(-1)                                  # [P, H, Lq]
         rel = self.u_p + 2 * self.d_s + 2 * E_EXP + (self.Lk + 2) * U32
-        self.env_o = TWO * (self.u * self.o.abs() + rel[..., None] * (self.p @ self.v.abs()))
+        if self.F is not None:
+            rel = rel + self.u_F
+        self.env_o = TWO * (self.u * self.o.abs() + rel[..., None] * (self.pF @ self.v.abs()))
         self.env_lse = self.d_s + E_EXP + 2.0 ** -23 * self.lse.abs()
 
     def backward(self, do, o_stored):
@@ -343,14 +364,25 @@ class Attn:
           dQ:    env = TWO * ( u |dQ| + scale ( sum_k E |K| + (Lk + 2) U32 sum_k |dS||K| ) )
           dK:    env = TWO * ( u |dK| + scale ( sum_q E |Q| + (Lq + 2) U32 sum_q |dS||Q| ) )
         A bias / table gradient is a sum of n entries of dS over problems and (query, key) cells:
-                 env = TWO * ( U32 |ref| + sum E + (n + 1) U32 sum |dS| )         (bias_grad_env)"""
+                 env = TWO * ( U32 |ref| + sum E + (n + 1) U32 sum |dS| )         (bias_grad_env)
+        With dropout (F of the class docstring, U_F = 3 U32):  dV = (P o F)^T dO,  dP = F o (dO V^T),  Delta and dS as above
+        (rowsum(dO o O) is still rowsum(P o dP)):
+          dV:    every p |dO| carries F, and the product p F is one operation more:  sum_q (r_p + u_p + (Lq + 2) U32 + U_F) p F |dO|
+          dP:    e_dP = F (D + 1) U32 sum_d |dO||V| + U_F |dP|                        (a dropped cell has dP = 0 and e_dP = 0 exactly)
+        and E, dQ, dK and the bias gradients follow from that dS unchanged.  On a fully dropped row o_stored = 0, so Delta = e_D = 0,
+        dP = e_dP = 0: dS = E = 0 and env_dq = 0 exactly, and the row adds exactly nothing to env_dk / env_dv."""
         DO, O = f64(do), f64(o_stored)
         r_p = (self.d_s + E_EXP + self.env_lse)[..., None]
-        pT = self.p.transpose(-1, -2)
-        self.dv = pT @ DO
-        self.env_dv = TWO * (self.u * self.dv.abs() + ((r_p + self.u_p + (self.Lq + 2) * U32) * self.p).transpose(-1, -2) @ DO.abs())
+        self.dv = self.pF.transpose(-1, -2) @ DO
+        r_v = r_p + self.u_p + (self.Lq + 2) * U32
+        if self.F is not None:
+            r_v = r_v + self.u_F
+        self.env_dv = TWO * (self.u * self.dv.abs() + (r_v * self.pF).transpose(-1, -2) @ DO.abs())
         dP = DO @ self.v.transpose(-1, -2)
         e_dP = (self.D + 1) * U32 * (DO.abs() @ self.v.abs().transpose(-1, -2))
+        if self.F is not None:
+            dP = self.F * dP
+            e_dP = self.F * e_dP + self.u_F * dP.abs()
         delta = (DO * O).sum(-1, keepdim=True)
         e_D = (self.D + 1) * U32 * (DO * O).abs().sum(-1, keepdim=True)
         self.ds = self.p * (dP - delta)

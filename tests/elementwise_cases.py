@@ -479,3 +479,194 @@ def cross_case(case, impl, with_bias, family):
     if with_bias:
         extra = [("dbias", dbias, *A.bias_grad_env(lambda t: t.sum(0)), dict(names=("head", "query", "key")))]
     return _attn_checks(f"{family} {_dt(dt)} B{B} Lq{Lq} Lk{Lk} h{nH} d{D}", A, got, lq, lk, family, extra)
+
+
+# ======================================================================================================= attention dropout and the generic window path
+# The dropout variants (vtx_attention_*_drop, vtx_srattn_*_drop, vtx_xattn_*_drop) and vtx_attention_fwd / _bwd with swin != 0 (the generic
+# attn_*_kernel with HAS_BIAS, the byte mask, the slab reduce and the CSR scatter of drel_pos).  Every driver takes ``drop`` = None or
+# (p, "explicit" | "hashed"): explicit = a keep mask drawn on the host with planted rows; hashed = the kernels' own counter-based hash, whose
+# decisions impl.keep_mask exports and the reference takes as its keep.
+P_DROP = 0.25
+DROP_SEED = 0x5DEECE66D2B79F31                       # both 32-bit halves are used by the hash
+MODES = ("explicit", "hashed")
+
+
+def hash_keep_mask(nprob, Lq, Lk, p, seed):
+    """The keep decisions of csrc/vtx_common.h drop_hash / drop_args in integer arithmetic on the host: uint8 [nprob, Lq, Lk]."""
+    M = 0xFFFFFFFF
+    p32 = float(torch.tensor(float(p), dtype=torch.float32))
+    thresh = min(int(p32 * 4294967296.0), M)
+    s0, s1 = seed & M, (seed >> 32) & M
+    prob = torch.arange(nprob, dtype=torch.int64)[:, None]
+    cell = torch.arange(Lq * Lk, dtype=torch.int64)[None, :]
+    h = (s0 ^ ((prob * 0x9E3779B1) & M))
+    h = h ^ (h >> 15); h = (h * 0x85EBCA6B) & M; h = h ^ (h >> 13)
+    h = (h + ((cell * 0xC2B2AE35) & M) + s1) & M
+    h = h ^ (h >> 16); h = (h * 0x27D4EB2F) & M; h = h ^ (h >> 15); h = (h * 0x165667B1) & M; h = h ^ (h >> 16)
+    return (h >= thresh).to(torch.uint8).reshape(nprob, Lq, Lk)
+
+
+def explicit_keep(P, H, Lq, Lk, p, seed, masked=None):
+    """uint8 [P, H, Lq, Lk] drawn with a seeded generator, and the planted rows: the LAST query of the last (problem, head) drops every
+    key, query 0 of (0, 0) keeps every key and -- ``masked`` [P, Lq, Lk] bool, shifted windows -- one row keeps exactly its masked keys
+    (every probability the row keeps is zero: o and the gradients vanish, lse stays finite).  -> keep, [(problem, head, query)] the rows
+    that must come out as exact zeros."""
+    g = torch.Generator().manual_seed(seed)
+    keep = (torch.rand((P, H, Lq, Lk), generator=g) >= p).to(torch.uint8)
+    keep[P - 1, H - 1, Lq - 1] = 0
+    keep[0, 0, 0] = 1
+    zero_rows = [(P - 1, H - 1, Lq - 1)]
+    if masked is not None:
+        part = masked.any(-1) & ~masked.all(-1)                                   # rows with some, not all, keys masked
+        part[0, 0] = part[P - 1, Lq - 1] = False                                  # (not the two rows planted above)
+        pw, qw = (int(i) for i in part.nonzero()[0])
+        keep[pw, H - 1, qw] = masked[pw, qw].to(torch.uint8)
+        zero_rows.append((pw, H - 1, qw))
+    return keep, zero_rows
+
+
+def drop_setup(impl, drop, P, H, Lq, Lk, masked=None, seed=DROP_SEED):
+    """-> (the impl's drop argument (p, seed, keep uint8 [P H, Lq, Lk] or None), the reference's keep [P, H, Lq, Lk], planted zero rows)."""
+    if drop is None:
+        return None, None, []
+    p, mode = drop
+    if mode == "explicit":
+        keep, rows = explicit_keep(P, H, Lq, Lk, p, 97, masked)
+        return (p, seed, keep.reshape(P * H, Lq, Lk).contiguous()), keep, rows
+    keep = impl.keep_mask(P * H, Lq, Lk, p, seed).cpu().reshape(P, H, Lq, Lk)
+    return (p, seed, None), keep, []
+
+
+def zero_row_checks(tag, A, got, planted, need_both=False):
+    """Rows whose every cell has p F = 0 (all keys dropped, or only masked keys kept): the envelope is zero there by construction, and the
+    kernel's o and dq must be EXACT zeros (a kernel normalising after the drop divides 0 by 0 there).  ``planted`` rows must be among them
+    -- a condition on the input, checked first."""
+    rows = (A.pF == 0).all(-1)                                                     # [P, H, Lq]
+    for r in planted:
+        assert bool(rows[r]), f"{tag}: the planted row {r} is not an empty row of the reference"
+    if need_both:
+        assert bool(rows.any()) and bool((~rows).any()), f"{tag}: the mask must hold empty and non-empty rows"
+    if not bool(rows.any()):
+        return 0
+    assert bool((A.env_o[rows] == 0).all()) and bool((A.env_dq[rows] == 0).all()) and bool((A.o[rows] == 0).all()) and bool((A.dq[rows] == 0).all())
+    for name in ("o", "dq"):
+        g = E.f64(got[name])[rows]
+        if not bool((g == 0).all()):
+            idx = tuple(int(i) for i in rows.nonzero()[int((g != 0).any(-1).nonzero()[0])])
+            raise E.ElementwiseError(f"{tag} {name}: the empty row (problem, head, query) = {idx} is not exactly zero", int((g != 0).sum()),
+                                     float("inf"), idx, "", (g != 0).nonzero())
+    return int(rows.sum())
+
+
+def _mode(drop):
+    return "" if drop is None else f" p{drop[0]} {drop[1]}"
+
+
+# ---- global attention with dropout: attn_*_kernel<T, D, NKT, DROP> at both sides of every ATTN_DISPATCH boundary (D = 64: NKT = 4 up to 64 tokens,
+# 14 up to 224; D = 32: NKT = 4 up to 64, 10 up to 160) -- bf16 / D = 64 included, which no dropout-free call reaches -- and the key-block kernels
+DROP_GLOBAL_SHAPES = [(2, 5, 2, 64), (1, 64, 2, 64), (1, 65, 2, 64), (2, 197, 2, 64), (1, 224, 2, 64), (1, 37, 2, 32), (1, 64, 3, 32), (1, 65, 2, 32), (1, 160, 2, 32)]
+DROP_LONG_SHAPES = [(1, 225, 2, 64), (1, 300, 2, 64), (1, 300, 3, 32)]
+DROP_GLOBAL_CASES = ([(dt, s, P_DROP, m) for dt in (F32, BF) for s in DROP_GLOBAL_SHAPES for m in MODES]
+                     + [(dt, (2, 37, 3, 64), p, m) for dt in (F32, BF) for p in (P_DROP, 0.9, 0.02) for m in MODES])
+DROP_LONG_CASES = ([(dt, s, P_DROP, m) for dt in (F32, BF) for s in DROP_LONG_SHAPES for m in MODES]
+                   + [(dt, (1, 225, 2, 64), p, m) for dt in (F32, BF) for p in (0.9, 0.02) for m in MODES])
+
+
+def global_drop_case(case, impl, family):
+    """impl.global_attn(qkv, do, B, L, nH, D, drop=(p, seed, keep)) -> o, lse, dqkv;  impl.keep_mask(nprob, Lq, Lk, p, seed) -> uint8 [nprob, Lq, Lk]"""
+    dt, (B, L, nH, D), p, mode = case
+    qkv, do = mk((B, L, 3 * nH * D), 61, dt), mk((B, L, nH * D), 62, dt)
+    darg, keep, planted = drop_setup(impl, (p, mode), B, nH, L, L)
+    o, lse, dqkv = impl.global_attn(qkv, do, B, L, nH, D, drop=darg)
+    q, k, v = E.split_qkv(qkv, B, L, nH, D)
+    A = E.Attn(q, k, v, D ** -0.5, None, dt == BF, dt, keep=keep, drop_p=p).backward(E.split_heads(do, nH), E.split_heads(E.f64(o), nH))
+    dq, dk, dv = E.split_qkv(E.f64(dqkv), B, L, nH, D)
+    got = dict(o=E.split_heads(E.f64(o), nH), lse=E.f64(lse).reshape(B, nH, L), dq=dq, dk=dk, dv=dv)
+    lq = dict(names=("image", "head", "query", "d"), tiles=dict(query=16))
+    lk = dict(names=("image", "head", "key", "d"), tiles=dict(key=16))
+    tag = f"{family} {_dt(dt)} B{B} L{L} h{nH} d{D}{_mode((p, mode))}"
+    w = _attn_checks(tag, A, got, lq, lk, family)
+    zero_row_checks(tag, A, got, planted)
+    return w
+
+
+# ---- the generic window path (vtx_attention_fwd / _bwd, swin != 0), without and with dropout
+# (B, H, win, shift, nH, D, bias): 7 x 7 on 14 x 14 shifted (bias + mask) and unshifted; D = 64; 12 x 12 on 24 x 24 (L = 144: NKT = 10, the
+# register-resident bias gradient at its widest); no bias (Twins local); 5 x 5 on 10 x 10 (a padded key tile)
+WINDOW_GENERIC_SHAPES = [(2, 14, 7, True, 3, 32, True), (2, 14, 7, False, 3, 32, True), (2, 14, 7, True, 2, 64, True), (1, 24, 12, True, 2, 32, True),
+                         (2, 14, 7, False, 2, 32, False), (3, 10, 5, True, 2, 32, True)]
+WINDOW_GENERIC_CASES = [(dt, s) for dt in (F32, BF) for s in WINDOW_GENERIC_SHAPES]
+DROP_WINDOW_CASES = ([(dt, s, P_DROP, m) for dt in (F32, BF) for s in WINDOW_GENERIC_SHAPES for m in MODES]
+                     + [(dt, WINDOW_GENERIC_SHAPES[5], p, m) for dt in (F32, BF) for p in (0.9, 0.02) for m in MODES])
+
+
+def window_generic_case(case, impl, family, drop=None):
+    """impl.window_generic(qkv, do, rel, pos, mask, B, H, win, shift, nH, D, drop) -> o (B, H, H, nH D), lse [B nW nH L], dqkv, drel [ntab, nH]
+    or None; rel = None: no bias (and then no mask)."""
+    dt, (B, H, win, shift, nH, D, with_bias) = case
+    L, nW = win * win, (H // win) ** 2
+    pos, mask, ntab = window_tables(H, win, shift, False)
+    if not with_bias:
+        assert not shift
+    qkv, do = mk((B, H, H, 3 * nH * D), 71, dt), mk((B, H, H, nH * D), 72, dt)
+    rel = mk((ntab, nH), 73, F32, 0.5) if with_bias else None
+    masked = mask.repeat(B, 1, 1) if mask is not None else None                  # [B nW, L, L]
+    darg, keep, planted = drop_setup(impl, drop, B * nW, nH, L, L, masked)
+    o, lse, dqkv, drel = impl.window_generic(qkv, do, rel, pos, mask, B, H, win, shift, nH, D, darg)
+    W_ = lambda t: E.to_windows(E.f64(t), B, H, H, win, shift, nH)
+    q, k, v = (W_(qkv[..., i * nH * D:(i + 1) * nH * D]) for i in range(3))
+    add = E.window_add(rel, pos, mask, B) if with_bias else None
+    A = E.Attn(q, k, v, D ** -0.5, add, dt == BF, dt, keep=keep, drop_p=drop[0] if drop else 0.0).backward(W_(do), W_(o))
+    dq, dk, dv = (W_(dqkv[..., i * nH * D:(i + 1) * nH * D]) for i in range(3))
+    got = dict(o=W_(o), lse=E.f64(lse).reshape(-1, nH, L), dq=dq, dk=dk, dv=dv)
+    lq = dict(names=("problem", "head", "query", "d"), split=dict(problem=("image", "window", nW)), tiles=dict(query=16))
+    lk = dict(names=("problem", "head", "key", "d"), split=dict(problem=("image", "window", nW)), tiles=dict(key=16))
+    extra = []
+    if with_bias:
+        extra = [("drel_pos", drel, *A.bias_grad_env(lambda t: rel_reduce(t, pos, ntab)), dict(names=("table entry", "head")))]
+    tag = f"{family} {_dt(dt)} B{B} {H}x{H} w{win} s{int(shift)} h{nH} d{D}{'' if with_bias else ' no bias'}{_mode(drop)}"
+    w = _attn_checks(tag, A, got, lq, lk, family, extra)
+    zero_row_checks(tag, A, got, planted)
+    return w
+
+
+# ---- sub-sampled attention (srattn_*_kernel<T, D, DROP> up to 64 keys, the key-block kernels beyond) and cross attention with a score bias
+DROP_SR_SHAPES = [(2, Lq, Lk, 2, D) if Lq < 300 else (1, Lq, Lk, 2, D) for D in (64, 32) for (Lq, Lk) in
+                  [(50, 50), (196, 49), (64, 7), (64, 64), (64, 65), (300, 145)]]
+SR_EMPTY = (2, 64, 7, 2, 64)                                                       # hashed at p = 0.9: about half of its rows come out empty
+DROP_SR_CASES = ([(dt, s, P_DROP, m) for dt in (F32, BF) for s in DROP_SR_SHAPES for m in MODES]
+                 + [(dt, SR_EMPTY, p, m) for dt in (F32, BF) for p in (0.9, 0.02) for m in MODES])
+DROP_CROSS_SHAPES = [(2, 49, 169, 2, 32), (2, 16, 36, 3, 32), (2, 49, 169, 2, 64), (3, 16, 36, 2, 64)]
+DROP_CROSS_CASES = ([(dt, s, P_DROP, m) for dt in (F32, BF) for s in DROP_CROSS_SHAPES for m in MODES]
+                    + [(dt, (2, 16, 36, 3, 32), p, m) for dt in (F32, BF) for p in (0.9, 0.02) for m in MODES])
+
+
+def cross_drop_case(case, impl, with_bias, family):
+    """impl.sr_attn(q, kv, do, B, Lq, Lk, nH, drop=) -> o, lse, dq, dkv;  impl.cross_attn(q, kv, do, bias, B, Lq, Lk, nH, drop=) -> .., dbias"""
+    dt, (B, Lq, Lk, nH, D), p, mode = case
+    C = nH * D
+    q, kv, do = mk((B, Lq, C), 81, dt), mk((B, Lk, 2 * C), 82, dt), mk((B, Lq, C), 83, dt)
+    bias = mk((nH, Lq, Lk), 84, F32, 0.5) if with_bias else None
+    tag = f"{family} {_dt(dt)} B{B} Lq{Lq} Lk{Lk} h{nH} d{D}{_mode((p, mode))}"
+    darg, keep, planted = drop_setup(impl, (p, mode), B, nH, Lq, Lk)
+    need_both = mode == "hashed" and p == 0.9 and (B, Lq, Lk, nH, D) == SR_EMPTY
+    if need_both:                                                                  # a condition on the INPUT, before any kernel output exists
+        empty = (keep == 0).all(-1)
+        assert bool(empty.any()) and bool((~empty).any()), f"{tag}: the exported mask must hold empty and non-empty rows"
+    if with_bias:
+        o, lse, dq, dkv, dbias = impl.cross_attn(q, kv, do, bias, B, Lq, Lk, nH, drop=darg)
+    else:
+        o, lse, dq, dkv = impl.sr_attn(q, kv, do, B, Lq, Lk, nH, drop=darg)
+    sh = lambda t: E.split_heads(E.f64(t).reshape(B, -1, C), nH)
+    A = E.Attn(sh(q), sh(kv[..., :C]), sh(kv[..., C:]), D ** -0.5, None if bias is None else E.f64(bias)[None], dt == BF, dt,
+               keep=keep, drop_p=p).backward(sh(do), sh(o))
+    dkv = E.f64(dkv).reshape(B, Lk, 2 * C)
+    got = dict(o=sh(o), lse=E.f64(lse).reshape(B, nH, Lq), dq=sh(dq), dk=sh(dkv[..., :C]), dv=sh(dkv[..., C:]))
+    lq = dict(names=("image", "head", "query", "d"), tiles=dict(query=16))
+    lk = dict(names=("image", "head", "key", "d"), tiles=dict(key=16))
+    extra = []
+    if with_bias:
+        extra = [("dbias", dbias, *A.bias_grad_env(lambda t: t.sum(0)), dict(names=("head", "query", "key")))]
+    w = _attn_checks(tag, A, got, lq, lk, family, extra)
+    zero_row_checks(tag, A, got, planted, need_both)
+    return w

@@ -609,8 +609,9 @@ int vtx_attention_fwd(const void* qkv, void* o, float* lse, const float* bias, c
   return attention_fwd_impl(qkv, o, lse, bias, mask, B, L, nH, D, swin, H, W, win, shift, dtype, (hipStream_t)stream, nullptr);
 }
 
-/* The same with dropout of the attention probabilities (training mode of the reference's F.dropout(attn, p)): register-resident
- * kernels only (L <= 224 with head dim 64, L <= 64 with head dim 32). */
+/* The same with dropout of the attention probabilities (training mode of the reference's F.dropout(attn, p)): the register-resident
+ * kernels of ATTN_DISPATCH (L <= 224 with head dim 64, L <= 160 with head dim 32; VTX_ERR_SHAPE beyond) and, for global attention
+ * without bias and mask at L > 224, the key-block kernels of attention_long.hip. */
 int vtx_attention_fwd_drop(const void* qkv, void* o, float* lse, const float* bias, const uint8_t* mask, int B, int L,
                            int nH, int D, int swin, int H, int W, int win, int shift, int dtype, float drop_p, uint64_t seed,
                            const uint8_t* keep, void* stream) {
