@@ -606,6 +606,24 @@ int vtx_adamw_step(int n, float* const* p, const float* const* g, float* const* 
  * HOST arrays of device pointers (train_dino.py:258-263, train_util.py:70-76). */
 int vtx_ema_update(int n, float* const* p, const float* const* g, const int64_t* numel, float m, void* stream);
 
+/* Model EMA (reference train_util.py:70-84 ``accumulate``, called from train.py:304-316), both weights from the caller:
+ *     e_i = fma(p_i, alpha, e_i * decay)        (one rounded product, then one fused multiply-add: mul_ then add_(alpha=))
+ * alpha is the CALLER's: the reference forms 1 - decay in double and rounds once (9.99999975e-06 for decay 0.99999, where the
+ * fp32 difference 1.f - decay of vtx_ema_update is 1.00135803e-05).  decay = 0 copies alpha * p (p itself for alpha = 1),
+ * decay = 1 with alpha = 0 leaves e unchanged: both exact for finite values.
+ *   vtx_ema_update2:    n pairs (e, p) as HOST arrays of device pointers (fp32, any 4-byte alignment), one pass.
+ *   vtx_adamw_ema_step: vtx_adamw_step with the EMA of the NEW parameter written in the same pass; ema = HOST array of n
+ *                       device pointers, a NULL entry = that tensor has no target.  p, m, v are bit-identical to
+ *                       vtx_adamw_step's, every target bit-identical to vtx_ema_update2 of the updated parameter.
+ *   vtx_opt_ema_pack:   tensors per launch of these two entries (their kernel arguments carry one address more per tensor). */
+int vtx_opt_ema_pack(void);
+int vtx_ema_update2(int n, float* const* e, const float* const* p, const int64_t* numel, float decay, float alpha,
+                    void* stream);
+int vtx_adamw_ema_step(int n, float* const* p, const float* const* g, float* const* m, float* const* v,
+                       const int64_t* numel, const float* lr, const float* wd, const float* norm, float max_norm,
+                       float beta1, float beta2, float eps, int t, void* stream, float* const* ema, float decay,
+                       float alpha);
+
 /* ---- DINO loss (csrc/dino.hip; reference loss.py:122-152): forward value and gradient w.r.t. the student logits in
  * one sweep, plus the teacher column sums of update_center.
  *   student [n_crop*B, K], teacher [2*B, K] (dtype), center [K] fp32 (read only); K % 8 == 0;

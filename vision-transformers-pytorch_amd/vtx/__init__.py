@@ -6,4 +6,14 @@
   vtx.nn          nn.Linear / nn.LayerNorm parameter containers with HIP forwards
   vtx.tables      integer window tables (pos / local_mask), bit-exact vs the reference
   vtx.ddp         data-parallel gradient all-reduce over RCCL on a side stream
+  vtx.optim       FusedAdamW (clip + AdamW + model EMA in one pass), ModelEma; vtx.accumulate = train_util.accumulate
 """
+
+
+def __getattr__(name):
+    # vtx.accumulate: the drop-in for the reference's train_util.accumulate (vtx.optim; imported on first use so that
+    # ``import vtx`` stays free of torch)
+    if name == "accumulate":
+        from .optim import accumulate
+        return accumulate
+    raise AttributeError(f"module 'vtx' has no attribute {name!r}")

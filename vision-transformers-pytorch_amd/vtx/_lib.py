@@ -213,6 +213,10 @@ _SIGNATURES = {
     "vtx_dinoaug_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "vtx_dinoaug_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "vtx_ema_update": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p]),
+    "vtx_opt_ema_pack": (c_int, []),
+    "vtx_ema_update2": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p]),
+    "vtx_adamw_ema_step": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_float, c_float]),
     "vtx_dino_loss_workspace": (c_size_t, [c_int, c_int]),
     "vtx_dino_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int,
                               c_int, c_int, c_float, c_float, c_float, c_int, c_void_p]),

@@ -100,11 +100,16 @@ def cancel_last_layer_grad(epoch, model, freeze):
 
 def dino_train_step(student, teacher, criterion, optimizer, crops, epoch, momentum, clip_grad_norm=3.0,
                     freeze_last_layer=1, autocast_dtype=torch.bfloat16, grad_accum=1, ddp=None, micro_step=None,
-                    ddp_sync="boundary"):
+                    ddp_sync="boundary", fuse_teacher=False):
     """One DINO micro-batch on a list of crops (2 global first, then the local ones) resident on the device.  Like the
     reference (train_dino.py:239-263) clip, cancel_last_layer_grad, the optimizer step, zero_grad and the momentum
-    update run only when ``(micro_step + 1) % grad_accum == 0``."""
-    from .optim import FusedAdamW
+    update run only when ``(micro_step + 1) % grad_accum == 0``.
+
+    ``fuse_teacher``: the teacher's momentum update rides in the optimizer pass (``FusedAdamW.step(ema=)``), with the
+    reference's weights (``1 - momentum`` formed in double, ``ops.ema_weights``); teacher parameters whose student
+    counterpart has no gradient (the last layer while it is frozen) take the standalone launch.  False (default): the step
+    is exactly what it is without this argument (``momentum_update``: ``1.f - m`` on the device)."""
+    from .optim import FusedAdamW, ModelEma
     from .train_step import accumulation_boundary, backward_ddp
     boundary = accumulation_boundary(grad_accum, micro_step)
     side = None
@@ -133,6 +138,33 @@ def dino_train_step(student, teacher, criterion, optimizer, crops, epoch, moment
     if ddp is not None:
         ddp.finish()
     params = ddp.parameters if ddp is not None else [p for p in student.parameters() if p.requires_grad]
+    if fuse_teacher:
+        # The teacher is written by MAIN-stream kernels here (inside the AdamW pass and the standalone launch), as it is by
+        # momentum_update: the teacher stream's wait_stream(main) at the top of the next call orders the next teacher
+        # forward after this write.  Keep it on the main stream.
+        me = getattr(optimizer, "_vtx_teacher_ema", None)
+        if me is None or me.model_ema is not teacher or me.model is not student:
+            # positional pairing, as the reference: zip(student.parameters(), teacher.parameters())
+            me = ModelEma.from_pairs(list(teacher.parameters()), list(student.parameters()))
+            me.model_ema, me.model = teacher, student
+            optimizer._vtx_teacher_ema = me
+        ema = (me, momentum)
+        if isinstance(optimizer, FusedAdamW):
+            if epoch < freeze_last_layer and clip_grad_norm and clip_grad_norm > 0:
+                torch.nn.utils.clip_grad_norm_(params, clip_grad_norm)      # (reference order: see below)
+                cancel_last_layer_grad(epoch, student, freeze_last_layer)
+                optimizer.step(ema=ema)
+            else:
+                cancel_last_layer_grad(epoch, student, freeze_last_layer)
+                optimizer.step(max_grad_norm=clip_grad_norm or 0.0, ema=ema)
+        else:
+            if clip_grad_norm and clip_grad_norm > 0:
+                torch.nn.utils.clip_grad_norm_(params, clip_grad_norm)
+            cancel_last_layer_grad(epoch, student, freeze_last_layer)
+            optimizer.step()
+            me.update(momentum)
+        optimizer.zero_grad(set_to_none=True)
+        return loss
     if isinstance(optimizer, FusedAdamW):
         if epoch < freeze_last_layer and clip_grad_norm and clip_grad_norm > 0:
             # reference order: clip over ALL gradients first, then the last layer's are dropped (train_dino.py:246-250)

@@ -985,6 +985,71 @@ def ema_update(targets, sources, momentum):
           "vtx_ema_update")
 
 
+def ema_weights(decay):
+    """(decay, alpha) as the model-EMA kernels get them: fp32(decay) and fp32(1 - decay) with the subtraction in DOUBLE, as
+    the reference's ``mul_(decay).add_(p, alpha=1 - decay)`` forms it (train_util.py:76).  Not ``1.f - fp32(decay)``, which
+    is what vtx_ema_update computes on the device: for decay 0.99999 that is 1.00135803e-05 against 9.99999975e-06."""
+    decay = float(decay)
+    return ctypes.c_float(decay).value, ctypes.c_float(1.0 - decay).value
+
+
+def ema_update2(targets, sources, decay, static=None):
+    """targets[i] = fma(sources[i], alpha, targets[i] * decay) with (decay, alpha) = ema_weights(decay): the reference's
+    ``accumulate`` over a list of fp32 tensor pairs, one launch per vtx_opt_ema_pack() pairs.
+    ``static`` = (target / source address arrays, numel array, count, total elements) of a caller that updates the same,
+    already validated, pairs every time (vtx.optim.ModelEma)."""
+    if static is None:
+        _dev(*targets, *sources)
+        n = len(targets)
+        if n == 0:
+            return
+        if len(sources) != n:
+            raise VtxError("vtx: ema_update2 needs as many sources as targets")
+        for t, s in zip(targets, sources):
+            if t.dtype != torch.float32 or s.dtype != torch.float32 or t.numel() != s.numel():
+                raise VtxError("vtx: ema_update2 needs fp32 tensor pairs of equal size "
+                               f"(got {t.dtype} {tuple(t.shape)} / {s.dtype} {tuple(s.shape)})")
+        ta, sa = _ptr_array(targets), _ptr_array(sources)
+        numel = (ctypes.c_int64 * n)(*[t.numel() for t in targets])
+        total = sum(t.numel() for t in targets)
+    else:
+        ta, sa, numel, n, total = static
+        if n == 0:
+            return
+    d, a = ema_weights(decay)
+    with _timed("ema2_kernel", 0.0, 12.0 * total):             # e, p read; e written
+        check(_lib.load().vtx_ema_update2(n, ta, sa, numel, d, a, _stream()), "vtx_ema_update2")
+
+
+def adamw_ema_step(params, grads, exp_avg, exp_avg_sq, lrs, wds, norm, max_norm, beta1, beta2, eps, t, ema_targets=None,
+                   decay=0.0, static=None):
+    """adamw_step with the model EMA of the updated parameters in the same pass (csrc/optim.hip adamw_step_kernel<true>):
+    ``ema_targets[i]`` (None: no target) = fma(p_i_new, alpha, ema_targets[i] * decay), (decay, alpha) = ema_weights(decay).
+    ``static`` = adamw_step's tuple followed by the target address array (NULL entries allowed) and the targets' total
+    element count."""
+    n = len(grads)
+    if static is None:
+        if ema_targets is None or len(ema_targets) != n or len(params) != n:
+            raise VtxError("vtx: adamw_ema_step needs one ema_targets entry (a tensor or None) per parameter")
+        _dev(*params, *grads, *exp_avg, *exp_avg_sq, norm, *ema_targets)
+        for p, e in zip(params, ema_targets):
+            if e is not None and (e.dtype != torch.float32 or p.dtype != torch.float32 or e.numel() != p.numel()):
+                raise VtxError("vtx: adamw_ema_step needs fp32 EMA targets of the parameter's size "
+                               f"(got {e.dtype} {tuple(e.shape)} for {p.dtype} {tuple(p.shape)})")
+        pa, ma, va = _ptr_array(params), _ptr_array(exp_avg), _ptr_array(exp_avg_sq)
+        ea = (ctypes.c_void_p * n)(*[None if e is None else e.data_ptr() for e in ema_targets])
+        numel = (ctypes.c_int64 * n)(*[p.numel() for p in params])
+        total = sum(p.numel() for p in params)
+        etotal = sum(e.numel() for e in ema_targets if e is not None)
+    else:
+        pa, ma, va, numel, total, ea, etotal = static
+    d, a = ema_weights(decay)
+    with _timed("adamw_step_kernel<ema>", 0.0, 28.0 * total + 8.0 * etotal):     # + e read, e written
+        check(_lib.load().vtx_adamw_ema_step(n, pa, _ptr_array(grads), ma, va, numel, (ctypes.c_float * n)(*lrs),
+                                             (ctypes.c_float * n)(*wds), _p(norm), float(max_norm), float(beta1),
+                                             float(beta2), float(eps), int(t), _stream(), ea, d, a), "vtx_adamw_ema_step")
+
+
 def dino_loss(student, teacher, center, n_crop, student_temp, teacher_temp, gscale=1.0):
     """DINO loss forward + gradient: -> (loss scalar tensor, dstudent, batch_center [K] fp32)."""
     _dev(student, teacher, center)

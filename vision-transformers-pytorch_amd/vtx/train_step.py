@@ -11,7 +11,7 @@ from torch import nn
 
 from . import functional as VF
 from .ops import VtxError
-from .optim import FusedAdamW
+from .optim import FusedAdamW, ModelEma
 
 
 class _MixLossFn(torch.autograd.Function):
@@ -118,7 +118,8 @@ def backward_ddp(loss, ddp, boundary, ddp_sync, fresh):
 
 
 def train_step(model, criterion, optimizer, batch, clip_grad_norm=5.0, autocast_dtype=torch.bfloat16,
-               grad_accum=1, ddp=None, micro_step=None, ddp_sync="boundary", loader_len=None, meter=None):
+               grad_accum=1, ddp=None, micro_step=None, ddp_sync="boundary", loader_len=None, meter=None,
+               model_ema=None, ema=0.0, ema_bn=False, ema_step=None):
     """One micro-batch of the reference's loop body (train.py:273-299).  ``batch`` = (input NCHW fp32, label1, label2,
     ratio) on the device.  Like the reference, clip + optimizer step + zero_grad run only on accumulation boundaries:
     ``(micro_step + 1) % grad_accum == 0`` (``micro_step`` = the loader index ``i``, required when grad_accum > 1) or, with
@@ -132,7 +133,20 @@ def train_step(model, criterion, optimizer, batch, clip_grad_norm=5.0, autocast_
     ``meter`` (vtx.metrics.DeviceMeter): the reference's log numbers of this micro-batch (train.py:277-281: prec@1 / prec@5
     of ``out`` against label1, and ``loss * grad_accum``) go to the device meter in one C call after the forward -- no
     ``.item()``, the host keeps running ahead.  None (default): the step is exactly what it is without this argument.
+
+    ``model_ema`` with ``ema > 0`` (``training.ema`` / ``training.ema_bn`` of the reference, train.py:304-316): after EVERY
+    micro-batch, boundary or not, ``model_ema = model_ema * d + model * (1 - d)`` with ``d = min(ema, (1 + t) / (10 + t))``
+    and ``t = ema_step`` (required: the reference's global count ``step + i``).  On a boundary with a ``FusedAdamW`` the
+    update rides in the AdamW pass (``step(ema=)``); otherwise it is ``ModelEma.update``: one launch per pack.  The pairing
+    (``vtx.optim.ModelEma``) is cached on the optimizer.  ``ema == 0`` or no ``model_ema``: the step is exactly what it is
+    without these arguments.
     """
+    me = decay = None
+    if model_ema is not None and ema > 0:
+        if ema_step is None:
+            raise ValueError("vtx: model_ema with ema > 0 needs ema_step (the global micro-batch count t of train.py:314)")
+        me = _model_ema(optimizer, model_ema, model, ema_bn)
+        decay = ModelEma.decay_at(ema, ema_step)
     x, l1, l2, ratio = batch
     boundary = accumulation_boundary(grad_accum, micro_step, loader_len)
     with torch.autocast("cuda", dtype=autocast_dtype, enabled=autocast_dtype is not None):
@@ -146,6 +160,8 @@ def train_step(model, criterion, optimizer, batch, clip_grad_norm=5.0, autocast_
     try:
         backward_ddp(loss, ddp, boundary, ddp_sync, fresh)
         if not boundary:
+            if me is not None:
+                me.update(decay)       # the parameters did not move, the EMA still does (train.py:304 is outside the boundary test)
             return loss
         if ddp is not None:
             ddp.finish()
@@ -154,11 +170,24 @@ def train_step(model, criterion, optimizer, batch, clip_grad_norm=5.0, autocast_
             ddp.reset()            # an abandoned backward must not leave reduced buckets / handed-out sinks behind
         raise
     if isinstance(optimizer, FusedAdamW):       # clip + AdamW in two multi-tensor HIP kernels (csrc/optim.hip)
-        optimizer.step(max_grad_norm=clip_grad_norm or 0.0)
+        if me is not None:
+            optimizer.step(max_grad_norm=clip_grad_norm or 0.0, ema=(me, decay))       # ... and the EMA in the AdamW pass
+        else:
+            optimizer.step(max_grad_norm=clip_grad_norm or 0.0)
     else:
         if clip_grad_norm and clip_grad_norm > 0:
             torch.nn.utils.clip_grad_norm_(ddp.parameters if ddp is not None else list(model.parameters()),
                                            clip_grad_norm)
         optimizer.step()
+        if me is not None:
+            me.update(decay)
     optimizer.zero_grad(set_to_none=True)
     return loss
+
+
+def _model_ema(optimizer, model_ema, model, ema_bn):
+    """The ModelEma of (model_ema, model), built once and kept on the optimizer."""
+    cached = getattr(optimizer, "_vtx_model_ema", None)
+    if cached is None or cached.model_ema is not model_ema or cached.model is not model or cached.ema_bn != bool(ema_bn):
+        cached = optimizer._vtx_model_ema = ModelEma(model_ema, model, bool(ema_bn))
+    return cached
