@@ -41,6 +41,7 @@ extern "C" {
 #define VTX_ERR_LAUNCH (-4)
 #define VTX_ERR_WORKSPACE (-5)
 #define VTX_ERR_NULL (-6)
+#define VTX_ERR_JPEG (-7)      /* not a supported JPEG (the reason is in VtxJpegInfo.reason), or an invalid decode plan */
 
 const char* vtx_strerror(int code);
 /* ABI version of the library (bumped on any signature change). */
@@ -568,6 +569,44 @@ size_t vtx_resample_workspace_bytes(int M, int S_h, int S_w);
 int vtx_resample_coeffs(int L, int S, int first, int n, void* table, void* stream);
 int vtx_resized_crop(const void* buf, size_t buf_bytes, const void* table, void* ws, size_t ws_bytes, void* out, int M, int S_h,
                      int S_w, void* stream);
+
+/* ---- Baseline JPEG decode, the first stage of the input pipeline (csrc/jpeg_host.h + csrc/jpeg.hip; SURVEY section 8 row F4;
+ * reference dataset.py:144, Image.open(buffer).convert("RGB")): bit-exact to PIL's decoder, i.e. libjpeg's default integer path
+ * (JDCT_ISLOW, fancy upsampling, table-driven YCbCr -> RGB).  The Huffman bit stream is decoded on the HOST into de-zigzagged
+ * int16 coefficient blocks (reentrant, no global state: one call per image from any thread); dequantisation, inverse DCT,
+ * chroma upsampling and colour conversion run on the device, two launches per batch; the pixels land as H x W x 3 uint8 rows in
+ * the byte buffer vtx_resized_crop reads.
+ * Accepted: SOF0 (or SOF1 with 8-bit tables), 8-bit, one interleaved scan, 1 component or YCbCr with luma sampling (1,1), (2,1)
+ * or (2,2) and chroma 1x1, restart intervals.  Refused with VTX_ERR_JPEG and a reason (VTX_JPEG_* of csrc/jpeg_host.h):
+ * 1 not a JPEG / malformed header, 2 progressive, 3 arithmetic, 4 lossless / hierarchical, 5 12-bit samples or 16-bit tables,
+ * 6 components other than 1 or 3, 7 other sampling factors, 8 more than one scan, 9 an Adobe transform other than YCbCr,
+ * 10 component ids R, G, B without JFIF, 11 DNL, 12 zero dimensions, 13 corrupt or truncated entropy-coded data, 14 a window
+ * outside the image or a coefficient range outside the caller's buffer, 15 more than 2^26 blocks or 2^28 pixels to store (the
+ * size functions return 0 for such an image or window, and for a VtxJpegInfo that no accepted header produces).
+ *   VtxJpegInfo: {int width, height, ncomp, hs, vs (luma sampling), mcux, mcuy, reason, restart, reserved[3]}
+ *   window = {row0, col0, rows, cols} in pixels, NULL = the whole image: only the MCUs the window touches, plus the one-sample
+ *     chroma context of the upsampling, are stored (the bit stream is still walked in full) and the device writes exactly
+ *     the window -- bit-equal to the full decode cropped.
+ *   plan record (vtx_jpeg_plan_bytes() = 480 bytes, csrc/jpeg_host.h VtxJpegPlan): geometry and sampling, the stored MCU
+ *     rectangle, the window, the byte offsets offs[3] = {coefficients, component planes, output pixels} given to
+ *     vtx_jpeg_entropy_decode, and the dequantisation table of each component (3 x 64 uint16, natural order).
+ * vtx_jpeg_entropy_decode: coef / coef_bytes = the caller's (pinned) coefficient memory; the image's blocks go to coef + offs[0]
+ *   (vtx_jpeg_coef_bytes(info, window) bytes: luma blocks row-major, then Cb, then Cr, 64 int16 each).  *reason may be NULL.
+ * vtx_jpeg_decode: coef = the DEVICE copy of that memory; plans = n records in HOST memory -- every record is checked against
+ *   coef_bytes, ws_bytes and out_bytes before anything is launched (VTX_ERR_JPEG for a record that would reach outside), then
+ *   copied to the head of ws on `stream` (pinned memory must stay unchanged until the stream has passed that copy); ws =
+ *   vtx_jpeg_workspace_bytes(n, P) device bytes, 8-byte aligned, P = the end of the records' plane ranges (each
+ *   vtx_jpeg_plane_bytes(info, window) bytes at offs[1], a multiple of 8); out: device bytes, image i's window as rows x cols x 3
+ *   uint8 at its offs[2]. */
+int vtx_jpeg_info(const void* data, size_t len, void* info);
+size_t vtx_jpeg_plan_bytes(void);
+size_t vtx_jpeg_coef_bytes(const void* info, const int* window);
+size_t vtx_jpeg_plane_bytes(const void* info, const int* window);
+size_t vtx_jpeg_workspace_bytes(int n, size_t plane_bytes);
+int vtx_jpeg_entropy_decode(const void* data, size_t len, const int* window, void* coef, size_t coef_bytes, const long long* offs,
+                            void* plan, int* reason);
+int vtx_jpeg_decode(const void* coef, size_t coef_bytes, const void* plans, int n, void* ws, size_t ws_bytes, void* out,
+                    size_t out_bytes, void* stream);
 
 /* ---- DINOAugment after the crop, on the device (csrc/dinoaug.hip; reference
  * transforms.py:225-294): RandomApply(ColorJitter) -> RandomGrayscale -> GaussianBlur -> Solarize per crop, one launch,

@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""Micro-benchmark of the JPEG decode stage (GPU box only): 128 PIL-encoded files of about 500 x 375, quality 90, 4:2:0
+(seeded smooth-plus-noise content), all measured in ONE run:
+  (a) PIL's full decode (Image.open(...).convert("RGB") to an array) on one core -- the yardstick;
+  (b) the host entropy stage (csrc/jpeg_host.h) on one core, and (c) on the default pool of 8 threads;
+  (d) the two device launches (csrc/jpeg.hip), coefficients already on the device;
+  (e) coefficient bytes against decoded bytes;
+  (f) DeviceMixPipeline(crop=...) end to end, from bytes and from decoded arrays.
+Writes the lines, with the commit, to --out (default profiles/jpeg_microbench.txt)."""
+import argparse
+import io
+import os
+import subprocess
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(REPO, "vision-transformers-pytorch_amd"), os.path.join(REPO, "tests")):
+    sys.path.insert(0, p)
+import numpy as np
+import torch
+
+import jpeg_np as J
+from vtx import ops
+from vtx.input_pipeline import DeviceMixPipeline, RandomResizedCropPlan
+
+dev = torch.device("cuda")
+
+
+def files(n=128):
+    from PIL import Image
+    out = []
+    for k in range(n):
+        h, w = (500 - k % 7, 375 - k % 5) if k % 4 == 1 else (375 - k % 5, 500 - k % 7)
+        b = io.BytesIO()
+        Image.fromarray(J.synth(h, w, 900 + k, noise=12)).save(b, "JPEG", quality=90, subsampling=2)
+        out.append(b.getvalue())
+    return out
+
+
+def wall_ms(fn, reps):
+    best = 1e30
+    for _ in range(3):
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        best = min(best, (time.perf_counter() - t0) / reps * 1e3)
+    return best
+
+
+def gpu_ms(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "jpeg_microbench.txt"))
+    ap.add_argument("--commit", default=None)
+    args = ap.parse_args()
+    commit = args.commit
+    if commit is None:
+        try:
+            commit = subprocess.run(["git", "-C", REPO, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
+        except OSError:
+            commit = ""
+    from PIL import Image
+    datas = files()
+    n = len(datas)
+    lines = [f"JPEG decode micro-benchmark, commit {commit or 'unknown'}: {n} PIL-encoded files of about 500 x 375, quality 90, 4:2:0, "
+             f"{sum(map(len, datas)) / n / 1024:.1f} KiB each; {torch.cuda.get_device_name(0)}"]
+
+    def pil_all():
+        for d in datas:
+            np.asarray(Image.open(io.BytesIO(d)).convert("RGB"))
+
+    pil = wall_ms(pil_all, 2)
+    lines.append(f"(a) PIL full decode, one core:              {pil:8.2f} ms per batch = {n / pil * 1e3:7.0f} images/s")
+    one = wall_ms(lambda: ops.jpeg_entropy_batch(datas), 2)
+    lines.append(f"(b) host entropy stage, one core:           {one:8.2f} ms per batch = {n / one * 1e3:7.0f} images/s "
+                 f"({pil / one:.2f} x PIL's full decode)")
+    pool = ThreadPoolExecutor(max_workers=8)
+    many = wall_ms(lambda: ops.jpeg_entropy_batch(datas, pool=pool), 3)
+    lines.append(f"(c) host entropy stage, pool of 8 threads:  {many:8.2f} ms per batch = {n / many * 1e3:7.0f} images/s")
+    coef, plans, infos, offs, end = ops.jpeg_entropy_batch(datas)
+    dcoef, pinned = coef.to(dev), plans.pin_memory()
+    out = torch.empty(end, dtype=torch.uint8, device=dev)
+    ops.jpeg_decode(dcoef, pinned, out)
+    torch.cuda.synchronize()
+    g = min(gpu_ms(lambda: ops.jpeg_decode(dcoef, pinned, out), 10) for _ in range(3))
+    lines.append(f"(d) device launches (inverse DCT + colour):  {g:8.3f} ms per batch = {n / g * 1e3:7.0f} images/s of GPU time")
+    lines.append(f"(e) coefficient bytes {coef.numel() / 1e6:.1f} MB against decoded bytes {end / 1e6:.1f} MB per batch "
+                 f"({coef.numel() / end:.2f} x); encoded {sum(map(len, datas)) / 1e6:.1f} MB")
+    arrays = [np.asarray(Image.open(io.BytesIO(d)).convert("RGB")) for d in datas]
+    labels = torch.arange(n, device=dev)
+    for name, images in (("bytes", datas), ("arrays", arrays)):
+        pipe = DeviceMixPipeline(crop=RandomResizedCropPlan(224, generator=torch.Generator().manual_seed(0)), seed=0)
+        for _ in range(3):
+            pipe(images, labels)
+        torch.cuda.synchronize()
+
+        def call():
+            pipe(images, labels)
+            torch.cuda.synchronize()
+
+        t = wall_ms(call, 5)
+        lines.append(f"(f) DeviceMixPipeline(crop=224) from {name:6s}: {t:8.2f} ms per batch wall = {n / t * 1e3:7.0f} images/s; "
+                     f"upload {pipe.upload_bytes / 1e6:.1f} MB")
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write(text)
+
+
+if __name__ == "__main__":
+    main()

@@ -96,6 +96,7 @@ const char* vtx_strerror(int code) {
     case VTX_ERR_LAUNCH: return "HIP kernel launch failed";
     case VTX_ERR_WORKSPACE: return "workspace too small";
     case VTX_ERR_NULL: return "required pointer is NULL";
+    case VTX_ERR_JPEG: return "not a supported JPEG (baseline, 8-bit, one interleaved scan, gray or YCbCr 4:4:4 / 4:2:2 / 4:2:0) or an invalid decode plan";
     default: return "unknown vtx error";
   }
 }

@@ -17,7 +17,7 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 #define VTX_WAVE 64
 
 enum { VTX_OK = 0, VTX_ERR_SHAPE = -1, VTX_ERR_DTYPE = -2, VTX_ERR_ALIGN = -3, VTX_ERR_LAUNCH = -4,
-       VTX_ERR_WORKSPACE = -5, VTX_ERR_NULL = -6 };
+       VTX_ERR_WORKSPACE = -5, VTX_ERR_NULL = -6, VTX_ERR_JPEG = -7 };
 enum { VTX_F32 = 0, VTX_BF16 = 1 };
 
 #ifndef VTX_PK_DS_GUARD

@@ -73,6 +73,11 @@ class SrLayerBwd(ctypes.Structure):
 ATTN_WINDOW, ATTN_GLOBAL = 1, 2
 
 
+class JpegInfo(ctypes.Structure):
+    """include/vtx.h VtxJpegInfo."""
+    _fields_ = [(n, _I) for n in ("width", "height", "ncomp", "hs", "vs", "mcux", "mcuy", "reason", "restart")] + [("reserved", _I * 3)]
+
+
 class TimerRec(ctypes.Structure):
     """include/vtx.h VtxTimerRec."""
     _fields_ = [("tag", _I), ("n", _I), ("k", _I), ("flags", _I), ("rows", _L), ("ms", _F)]
@@ -208,6 +213,13 @@ _SIGNATURES = {
     "vtx_resample_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "vtx_resample_coeffs": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vtx_resized_crop": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "vtx_jpeg_info": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "vtx_jpeg_plan_bytes": (c_size_t, []),
+    "vtx_jpeg_coef_bytes": (c_size_t, [c_void_p, c_void_p]),
+    "vtx_jpeg_plane_bytes": (c_size_t, [c_void_p, c_void_p]),
+    "vtx_jpeg_workspace_bytes": (c_size_t, [c_int, c_size_t]),
+    "vtx_jpeg_entropy_decode": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "vtx_jpeg_decode": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     "vtx_dinoaug_plan_bytes": (c_size_t, []),
     "vtx_dinoaug_max_box_radius": (c_int, []),
     "vtx_dinoaug_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -14,9 +14,15 @@ With ``randaug=RandAugmentPlan(...)`` the pipeline follows the reference's defau
 images (factory.py:184-187): PIL-style mix (``Image.blend`` / ``paste``), RandAugment (autoaugment.py:586-678, every op
 bit-exact to PIL; csrc/randaug.hip), then ToTensor / Normalize / RandomErasing as before.
 
-With ``crop=RandomResizedCropPlan(...)`` the pipeline starts from the DECODED images (a list of H x W x 3 uint8 arrays of
-any size): RandomResizedCrop(size, BICUBIC) + RandomHorizontalFlip (factory.py:170-171) run on the device
-(csrc/resample.hip, bit-exact to PIL's ``crop`` + ``resize``), fed by one asynchronous upload of the crops' pixels.
+With ``crop=RandomResizedCropPlan(...)`` the pipeline starts from the images as the dataset holds them: a list whose items
+are decoded images (H x W x 3 uint8 arrays of any size) or ENCODED baseline JPEGs (``bytes`` / ``bytearray``; reference
+dataset.py:144 decodes them with ``Image.open(buffer).convert("RGB")``), mixed freely.  RandomResizedCrop(size, BICUBIC) +
+RandomHorizontalFlip (factory.py:170-171) run on the device (csrc/resample.hip, bit-exact to PIL's ``crop`` + ``resize``), fed
+by one asynchronous upload of the crops' pixels.  An encoded item never exists decoded on the host: its Huffman stream is turned
+into coefficient blocks on a thread pool (csrc/jpeg_host.h; ``decode_threads``, default 8, at most 16), only the blocks the
+bounding rectangle of its crops needs are uploaded, and the device decodes them (csrc/jpeg.hip: dequantisation, inverse DCT,
+chroma upsampling, colour conversion, bit-exact to PIL's decoder) straight into the byte buffer the resample reads.  A file the
+decoder refuses (progressive, CMYK, ...) raises VtxError before anything is launched: decode it with PIL and pass the array.
 ``DeviceEvalPipeline`` is the validation transform (Resize + CenterCrop + ToTensor + Normalize, factory.py:215-222) and
 ``DeviceMultiCrop`` the crop stage of DINOAugment (transforms.py:249-279) on the same kernel.
 
@@ -27,6 +33,7 @@ operations behind them; the draws are ``DinoAugmentPlan``'s), then ToTensor + No
 import math
 import random as _random
 import struct
+from concurrent.futures import ThreadPoolExecutor
 
 import torch
 
@@ -260,6 +267,7 @@ class RandAugmentPlan:
         return code, p, f
 
 
+MAX_DECODE_THREADS = 16                           # entropy-decode pool of the crop stage (never sized by the machine's CPU count)
 MAX_TAPS = 65                                     # = vtx_resample_max_taps(): crop side / output side <= 16
 MAX_OUT_WIDTH = 840                               # the LDS tile of csrc/resample.hip holds 65 rows of the output's width
 
@@ -375,7 +383,9 @@ def check_crop_record(rec, h, w, out_hw):
 def pack_sources(images, records, alloc=None):
     """Pack the pixels the crops read into one byte buffer: per source image the bounding rectangle of the boxes that name
     it (a source no record names takes no room), rows contiguous.  ``alloc(nbytes)`` -> uint8 host tensor to fill (a pinned
-    staging buffer); default a fresh tensor.  -> (buffer, placed) with placed[s] = (offset, row0, col0, rows, cols)."""
+    staging buffer); default a fresh tensor.  -> (buffer, placed) with placed[s] = (offset, row0, col0, rows, cols).
+    An ``EncodedJpeg`` source gets its room BEHIND the decoded ones (the same rectangle is its decode window, which the device
+    decoder fills): ``buffer`` holds the decoded sources only."""
     rects = {}
     for rec in records:
         s = rec["source"]
@@ -383,15 +393,18 @@ def pack_sources(images, records, alloc=None):
         r = rects.get(s)
         rects[s] = (top, left, top + ch, left + cw) if r is None else (min(r[0], top), min(r[1], left), max(r[2], top + ch),
                                                                      max(r[3], left + cw))
-    placed, total = {}, 0
-    for s in sorted(rects):
+    placed, total, raw = {}, 0, 0
+    for s in sorted(rects, key=lambda s: (isinstance(images[s], EncodedJpeg), s)):     # decoded sources first
         r0, c0, r1, c1 = rects[s]
         placed[s] = (total, r0, c0, r1 - r0, c1 - c0)
         total += (r1 - r0) * (c1 - c0) * 3
-    buf = alloc(total) if alloc is not None else torch.empty(total, dtype=torch.uint8)
+        if not isinstance(images[s], EncodedJpeg):
+            raw = total
+    buf = alloc(raw) if alloc is not None else torch.empty(raw, dtype=torch.uint8)
     for s, (off, r0, c0, rows, cols) in placed.items():
-        buf[off:off + rows * cols * 3].view(rows, cols, 3).copy_(images[s][r0:r0 + rows, c0:c0 + cols])
-    return buf[:total], placed
+        if not isinstance(images[s], EncodedJpeg):
+            buf[off:off + rows * cols * 3].view(rows, cols, 3).copy_(images[s][r0:r0 + rows, c0:c0 + cols])
+    return buf[:raw], placed
 
 
 def pack_crop_table(records, placed):
@@ -406,14 +419,28 @@ def pack_crop_table(records, placed):
     return torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8)
 
 
+class EncodedJpeg:
+    """An item of ``images`` that came as ``bytes`` / ``bytearray``: an encoded JPEG.  Its header is parsed on the spot (a file
+    the decoder refuses raises VtxError here, before anything is launched -- the caller decodes such a file with PIL and
+    passes the array); ``shape`` is what the decoded array's would be."""
+
+    def __init__(self, data):
+        self.data, self.info = data, ops.jpeg_info(data)
+        self.shape = (self.info.height, self.info.width, 3)
+
+
 def _as_images(images):
-    """list of H x W x 3 uint8 host arrays / tensors -> list of tensors; raises for anything else."""
+    """list of H x W x 3 uint8 host arrays / tensors, or encoded JPEGs as bytes / bytearray -> list of tensors /
+    EncodedJpeg; raises for anything else."""
     out = []
     for im in images:
+        if isinstance(im, (bytes, bytearray, EncodedJpeg)):
+            out.append(im if isinstance(im, EncodedJpeg) else EncodedJpeg(im))
+            continue
         t = torch.as_tensor(im)
         if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.is_cuda or t.shape[0] < 1 or t.shape[1] < 1:
-            raise ops.VtxError(f"vtx: the crop stage takes decoded H x W x 3 uint8 host images (PIL's RGB layout), got "
-                               f"{t.dtype} {tuple(t.shape)}")
+            raise ops.VtxError(f"vtx: the crop stage takes decoded H x W x 3 uint8 host images (PIL's RGB layout) or encoded JPEG "
+                               f"bytes, got {t.dtype} {tuple(t.shape)}")
         out.append(t)
     if not out:
         raise ops.VtxError("vtx: empty batch of images")
@@ -484,26 +511,55 @@ class _CropStage(_UploadRing):
     """The crop stage the pipelines share: validate, pack and upload the pixels the crops read, launch the resample.
     ``crop_records`` holds the records of the last call (boxes, flips), ``upload_bytes`` the size of its upload."""
 
-    def __init__(self):
+    def __init__(self, decode_threads=8):
         super().__init__()
+        if not 1 <= int(decode_threads) <= MAX_DECODE_THREADS:
+            raise ValueError(f"decode_threads {decode_threads} outside 1..{MAX_DECODE_THREADS}")
+        self.decode_threads, self._pool = int(decode_threads), None
         self.crop_records, self.upload_bytes = [], 0
 
     def upload_crops(self, images, records, dev):
         """Validate the records, pack the pixels they read straight into a pinned staging buffer, one asynchronous upload
-        -> (device buffer, placed).  Raises before anything is launched."""
+        -> (device buffer, placed).  Raises before anything is launched.
+
+        Encoded sources: the decode window of each is the bounding rectangle of its boxes (``placed``'s rectangle); their
+        Huffman streams are decoded on the thread pool into a pinned coefficient buffer (only the blocks the window needs),
+        that is uploaded instead of pixels and the device decoder writes the windows behind the decoded sources' pixels in
+        the same device buffer."""
         for rec in records:
             h, w = images[rec["source"]].shape[:2]
             check_crop_record(rec, h, w, rec["out_hw"])
-        slot = []
+        slots = {}
 
-        def alloc(nbytes):
-            slot.extend(self._pinned(max(nbytes, 1), torch.uint8, "images"))
-            return slot[0]
+        def alloc(nbytes, kind="images"):
+            slots[kind] = self._pinned(max(nbytes, 1), torch.uint8, kind)
+            return slots[kind][0]
 
         host, placed = pack_sources(images, records, alloc)
-        buf = host.to(dev, non_blocking=True)
-        slot[1].record()
-        self.upload_bytes = host.numel()
+        enc = [s for s in placed if isinstance(images[s], EncodedJpeg)]
+        if not enc:
+            buf = host.to(dev, non_blocking=True)
+            slots["images"][1].record()
+            self.upload_bytes = host.numel()
+            return buf, placed
+        # The pool lives as long as the pipeline (its idle threads end with the interpreter).  When one file is refused the
+        # exception leaves pool.map while the batch's other jobs may still be writing their blocks: they write into the
+        # staging slot their closure keeps alive, and the slot's event is recorded only by a call that launches.
+        if self._pool is None and self.decode_threads > 1:
+            self._pool = ThreadPoolExecutor(max_workers=self.decode_threads, thread_name_prefix="vtx-jpeg")
+        coef, plans, _, offs, end = ops.jpeg_entropy_batch([images[s].data for s in enc], [placed[s][1:] for s in enc],
+                                                           lambda kind, nbytes: alloc(nbytes, kind), host.numel(), self._pool)
+        if offs != [placed[s][0] for s in enc]:
+            raise ops.VtxError("vtx: the decoder's output offsets do not match the packed layout of the sources")
+        buf = torch.empty(end, dtype=torch.uint8, device=dev)
+        if host.numel():
+            buf[:host.numel()].copy_(host, non_blocking=True)
+        slots["images"][1].record()
+        dcoef = coef.to(dev, non_blocking=True)
+        slots["coefs"][1].record()
+        ops.jpeg_decode(dcoef, plans, buf)
+        slots["jplans"][1].record()
+        self.upload_bytes = host.numel() + coef.numel()
         return buf, placed
 
     def run_crops(self, images, plans, dev, boxes=None):
@@ -550,12 +606,13 @@ class DeviceMixPipeline(_CropStage):
     is built (augmenting before the mix needs two independent augmentations per sample).
 
     ``crop``: a RandomResizedCropPlan.  ``images`` is then a list of decoded H x W x 3 uint8 host arrays or tensors of any
-    sizes; the pixels the crops read are packed into a pinned buffer and uploaded once, cropped / resized / flipped on the
+    sizes and / or encoded JPEGs (bytes / bytearray, decoded on the device; ``decode_threads`` host threads walk their Huffman
+    streams); the pixels the crops read are packed into a pinned buffer and uploaded once, cropped / resized / flipped on the
     device (csrc/resample.hip, bit-exact to PIL) into the uint8 batch, and the sequence above runs on that batch.  The
     crops of a batch are drawn first, image by image (``boxes`` = [(top, left, h, w, flip)] overrides the draws)."""
 
     def __init__(self, mixup=0.2, cutmix=1, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), erase=None, seed=None,
-                 output="nchw_fp32", randaug=None, mix_before_aug=True, crop=None):
+                 output="nchw_fp32", randaug=None, mix_before_aug=True, crop=None, decode_threads=8):
         if output not in ("nchw_fp32", "nhwc_bf16"):
             raise ValueError(output)
         if randaug is not None and not mix_before_aug:
@@ -565,7 +622,7 @@ class DeviceMixPipeline(_CropStage):
         self.randaug, self.crop = randaug, crop
         self.mean, self.std = torch.tensor(mean, dtype=torch.float32), torch.tensor(std, dtype=torch.float32)
         self.rng = _random.Random(seed) if seed is not None else _random
-        super().__init__()
+        super().__init__(decode_threads)
 
     def pack(self, plans):
         """-> (plan table uint8 [N * vtx_mix_plan_bytes()], fill table fp32 or None)"""
@@ -594,6 +651,9 @@ class DeviceMixPipeline(_CropStage):
             images = self.run_crops(images, [self.crop], labels.device, None if boxes is None else [[b] for b in boxes])[0]
         elif boxes is not None:
             raise ops.VtxError("vtx: boxes given to a pipeline without a crop plan")
+        elif not torch.is_tensor(images):
+            raise ops.VtxError("vtx: a pipeline without a crop plan takes a device batch (N, C, H, W); decoded images or encoded "
+                               "JPEGs need crop=RandomResizedCropPlan(...)")
         n, c, h, w = images.shape
         if self.randaug is not None and (images.dtype != torch.uint8 or c != 3):
             raise ops.VtxError(f"vtx: RandAugment works on uint8 RGB images (PIL's), got {images.dtype} with {c} channels")
@@ -617,14 +677,14 @@ class DeviceMixPipeline(_CropStage):
 class DeviceEvalPipeline(_CropStage):
     """The reference's validation transform (factory.py:215-222) from decoded images: Resize(valid_size + 32, BICUBIC) +
     CenterCrop(valid_size) on the device (csrc/resample.hip, bit-exact to PIL), then ToTensor + Normalize by the kernel of
-    the training pipeline with a trivial plan (no mix, no rectangles).  list of H x W x 3 uint8 host images -> the
-    normalised batch, ``output`` as in DeviceMixPipeline."""
+    the training pipeline with a trivial plan (no mix, no rectangles).  list of H x W x 3 uint8 host images and / or encoded
+    JPEGs (bytes, decoded on the device) -> the normalised batch, ``output`` as in DeviceMixPipeline."""
 
     def __init__(self, valid_size, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), output="nchw_fp32", resize=None,
-                 device="cuda"):
+                 device="cuda", decode_threads=8):
         if output not in ("nchw_fp32", "nhwc_bf16"):
             raise ValueError(output)
-        super().__init__()
+        super().__init__(decode_threads)
         self.plan, self.output, self.device = CenterCropPlan(valid_size, resize), output, torch.device(device)
         self.mean, self.std = torch.tensor(mean, dtype=torch.float32), torch.tensor(std, dtype=torch.float32)
         self._tables = {}                         # the trivial normalise plan per batch size, on the device
@@ -643,11 +703,12 @@ class DeviceMultiCrop(_CropStage):
     """The crop stage of a multi-crop augmentation (DINOAugment, reference transforms.py:249-279: 2 global crops of 224
     and 8 local crops of 96 per image, each a RandomResizedCrop(..., BICUBIC)): every source is uploaded once and read by
     all its crops.  ``plans`` = one RandomResizedCropPlan per crop; ``__call__(images)`` -> one uint8 (N, 3, S, S) device
-    batch per plan.  The draws run image by image, crop by crop.  DINOAugment's flip / ColorJitter / grayscale /
+    batch per plan (``images``: decoded arrays and / or encoded JPEGs as bytes, of which only the blocks under the crops are
+    uploaded and decoded on the device).  The draws run image by image, crop by crop.  DINOAugment's flip / ColorJitter / grayscale /
     GaussianBlur / solarize after the crop are ``DeviceDinoAugment``'s."""
 
-    def __init__(self, plans, device="cuda"):
-        super().__init__()
+    def __init__(self, plans, device="cuda", decode_threads=8):
+        super().__init__(decode_threads)
         self.plans, self.device = list(plans), torch.device(device)
 
     def __call__(self, images, boxes=None):
@@ -774,8 +835,8 @@ class DinoAugmentPlan:
 
 
 class DeviceDinoAugment(_CropStage):
-    """reference transforms.DINOAugment (transforms.py:216-294) from decoded images, on the device: list of N decoded
-    H x W x 3 uint8 host images -> list of 2 + n_local_crop normalised batches (N, 3, S, S), global crops first -- the list
+    """reference transforms.DINOAugment (transforms.py:216-294) from decoded images or encoded JPEGs, on the device: list of N
+    decoded H x W x 3 uint8 host images (or JPEG bytes, decoded on the device) -> list of 2 + n_local_crop normalised batches (N, 3, S, S), global crops first -- the list
     ``vtx.dino.dino_train_step`` takes.  One upload of the pixels the crops read, then per crop size three launches: crop +
     BICUBIC resize + flip (csrc/resample.hip), ColorJitter / grayscale / GaussianBlur / solarize (csrc/dinoaug.hip), ToTensor
     + Normalize (csrc/input.hip, the trivial plan); the uint8 stages are bit-exact to PIL.  ``output`` as in
@@ -786,10 +847,10 @@ class DeviceDinoAugment(_CropStage):
 
     def __init__(self, global_crop_size, local_crop_size, global_crop_scale, local_crop_scale, n_local_crop,
                  mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), output="nchw_fp32", generator=None, rng=None, seed=None,
-                 device="cuda"):
+                 device="cuda", decode_threads=8):
         if output not in ("nchw_fp32", "nhwc_bf16"):
             raise ValueError(output)
-        super().__init__()
+        super().__init__(decode_threads)
         if rng is None and seed is not None:
             rng = _random.Random(seed)
         self.plan = DinoAugmentPlan(global_crop_size, local_crop_size, global_crop_scale, local_crop_scale, n_local_crop,

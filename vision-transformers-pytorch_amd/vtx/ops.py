@@ -1160,6 +1160,146 @@ def resized_crop(buffer, table, out_hw):
     return out
 
 
+JPEG_REASONS = {1: "not a JPEG, or a malformed header", 2: "progressive (SOF2)", 3: "arithmetic coding", 4: "lossless or hierarchical",
+                5: "12-bit samples or 16-bit quantisation tables", 6: "neither 1 nor 3 components (CMYK / YCCK)",
+                7: "sampling factors other than 4:4:4 / 4:2:2 / 4:2:0", 8: "more than one scan",
+                9: "an Adobe marker declaring a transform other than YCbCr", 10: "component ids R, G, B without JFIF (an RGB file)",
+                11: "height given by a DNL marker", 12: "zero width or height", 13: "corrupt or truncated entropy-coded data",
+                14: "window outside the image, or coefficients outside the buffer",
+                15: "more than 2^26 blocks or 2^28 pixels to store (decode a smaller window)"}
+
+
+def _jpeg_ptr(data):
+    """bytes / bytearray -> what ctypes passes as const void*"""
+    if isinstance(data, bytes):
+        return data
+    if isinstance(data, bytearray):
+        return (ctypes.c_char * len(data)).from_buffer(data) if len(data) else None
+    raise VtxError(f"vtx: an encoded JPEG is bytes or bytearray, got {type(data).__name__}")
+
+
+def _jpeg_window(window):
+    return None if window is None else (ctypes.c_int * 4)(*[int(v) for v in window])
+
+
+def jpeg_plan_bytes():
+    return _lib.load().vtx_jpeg_plan_bytes()
+
+
+def jpeg_info(data, check=True):
+    """Host only: the headers of an encoded JPEG -> a filled _lib.JpegInfo (width, height, ncomp, hs, vs, mcux, mcuy, reason,
+    restart).  ``check``: raise VtxError for a file the decoder refuses (``reason`` != 0) instead of returning it."""
+    info = _lib.JpegInfo()
+    rc = _lib.load().vtx_jpeg_info(_jpeg_ptr(data), len(data), ctypes.byref(info))
+    if rc != 0 and (check or info.reason == 0):
+        raise VtxError(f"vtx_jpeg_info: not a supported JPEG: {JPEG_REASONS.get(info.reason, 'bad arguments')} "
+                       f"(code {rc}, reason {info.reason})")
+    return info
+
+
+def jpeg_coef_bytes(info, window=None):
+    """Bytes of the int16 coefficient blocks of the image restricted to ``window`` = (row0, col0, rows, cols)."""
+    return _lib.load().vtx_jpeg_coef_bytes(ctypes.byref(info), _jpeg_window(window))
+
+
+def jpeg_plane_bytes(info, window=None):
+    return _lib.load().vtx_jpeg_plane_bytes(ctypes.byref(info), _jpeg_window(window))
+
+
+def jpeg_entropy_decode(data, coef, offs, plan, window=None):
+    """Host only, releases the GIL: the Huffman bit stream of one encoded JPEG -> its coefficient blocks at byte ``offs[0]`` of
+    the host tensor ``coef`` and its plan record into the host uint8 tensor ``plan`` (jpeg_plan_bytes() bytes).  ``offs`` =
+    (coefficient, plane, output) byte offsets of the image in the three buffers of ``jpeg_decode``."""
+    if coef.is_cuda or plan.is_cuda or not coef.is_contiguous() or not plan.is_contiguous():
+        raise VtxError("vtx: jpeg_entropy_decode writes contiguous HOST tensors")
+    if plan.dtype != torch.uint8 or plan.numel() != jpeg_plan_bytes():
+        raise VtxError(f"vtx: the plan record is {jpeg_plan_bytes()} uint8 bytes")
+    reason = ctypes.c_int(0)
+    o = (ctypes.c_longlong * 3)(*[int(v) for v in offs])
+    rc = _lib.load().vtx_jpeg_entropy_decode(_jpeg_ptr(data), len(data), _jpeg_window(window), coef.data_ptr(),
+                                             coef.numel() * coef.element_size(), o, plan.data_ptr(), ctypes.byref(reason))
+    if rc != 0:
+        raise VtxError(f"vtx_jpeg_entropy_decode: not a supported JPEG: {JPEG_REASONS.get(reason.value, 'bad arguments')} "
+                       f"(code {rc}, reason {reason.value})")
+
+
+def jpeg_entropy_batch(datas, windows=None, alloc=None, out_base=0, pool=None):
+    """The host stage of a batch: headers, layout, entropy decode of every file (through ``pool.map`` when a thread pool is
+    given).  ``windows[i]`` = (row0, col0, rows, cols) or None; ``alloc(kind, nbytes)`` -> host uint8 tensor for kind "coefs" /
+    "jplans" (pinned staging memory; default fresh tensors); the images' pixels are laid out one after the other from byte
+    ``out_base`` of the output buffer.  Raises VtxError for a refused file.
+    -> (coef uint8 host tensor, plan table uint8 host tensor, [info], [output byte offset], output end)"""
+    n = len(datas)
+    windows = [None] * n if windows is None else windows
+    infos = [jpeg_info(d) for d in datas]
+    pb = jpeg_plan_bytes()
+    offs, co, po, oo = [], 0, 0, int(out_base)
+    for info, win in zip(infos, windows):
+        cb = jpeg_coef_bytes(info, win)
+        if cb == 0:
+            raise VtxError(f"vtx: JPEG decode window {win} outside the {info.height} x {info.width} image, or more than 2^26 blocks "
+                           f"/ 2^28 pixels to store (nothing is allocated for such a file)")
+        rows, cols = (info.height, info.width) if win is None else (win[2], win[3])
+        offs.append((co, po, oo))
+        co, po, oo = co + cb, po + cb // 2, oo + rows * cols * 3
+    alloc = alloc or (lambda kind, nbytes: torch.empty(nbytes, dtype=torch.uint8))
+    coef, plans = alloc("coefs", max(co, 1))[:max(co, 1)], alloc("jplans", n * pb)[:n * pb]
+    job = lambda i: jpeg_entropy_decode(datas[i], coef, offs[i], plans[i * pb:(i + 1) * pb], windows[i])
+    list(pool.map(job, range(n)) if pool is not None and n > 1 else map(job, range(n)))
+    return coef[:co], plans, infos, [o[2] for o in offs], oo
+
+
+def _jpeg_plan_fields(plans):
+    """host plan table -> (blocks, pixels, coef_off, ws_off, out_off) int64 numpy arrays, for sizing only (the library
+    checks every record itself)."""
+    pb = jpeg_plan_bytes()
+    raw = plans.numpy().reshape(-1, pb)
+    i32 = raw[:, :64].copy().view("<i4")
+    i64 = raw[:, 64:96].copy().view("<i8")
+    per = i32[:, 3].astype("int64") * i32[:, 4] + 2
+    per[i32[:, 2] != 3] = 1
+    blocks = i32[:, 9].astype("int64") * i32[:, 10] * per
+    return blocks, i32[:, 13].astype("int64") * i32[:, 14], i64[:, 0], i64[:, 1], i64[:, 2]
+
+
+def jpeg_decode(coef, plans, out=None):
+    """The device stage of the JPEG decoder, two launches for the batch (csrc/jpeg.hip), bit-exact to PIL: ``coef`` = the device
+    copy of the coefficient bytes, ``plans`` = the HOST plan table of ``jpeg_entropy_batch`` (uint8).  Image i's window lands as
+    rows x cols x 3 uint8 at its output offset of ``out`` (a uint8 device buffer; default a fresh one that ends with the last
+    image).  A pageable plan table is waited for; a pinned one must stay unchanged until the stream has copied it.
+    -> ``out``"""
+    _dev(coef)
+    pb = jpeg_plan_bytes()
+    if plans.is_cuda or plans.dtype != torch.uint8 or not plans.is_contiguous() or plans.numel() == 0 or plans.numel() % pb:
+        raise VtxError(f"vtx: jpeg_decode takes a contiguous uint8 HOST table of {pb}-byte records")
+    n = plans.numel() // pb
+    blocks, pixels, _, ws_off, out_off = _jpeg_plan_fields(plans)
+    if out is None:
+        out = torch.empty(max(int((out_off + 3 * pixels).max()), 1), dtype=torch.uint8, device=coef.device)
+    _dev(out)
+    if out.dtype != torch.uint8:
+        raise VtxError("vtx: jpeg_decode writes a uint8 device buffer")
+    lib = _lib.load()
+    nws = lib.vtx_jpeg_workspace_bytes(n, max(int((ws_off + 64 * blocks).max()), 0))
+    ws = torch.empty((nws + 7) // 8, dtype=torch.int64, device=coef.device)
+    check(lib.vtx_jpeg_decode(_p(coef), coef.numel() * coef.element_size(), plans.data_ptr(), n, _p(ws), nws, _p(out), out.numel(),
+                              _stream()), "vtx_jpeg_decode")
+    if not plans.is_pinned():
+        torch.cuda.current_stream().synchronize()
+    return out
+
+
+def jpeg_decode_images(datas, windows=None, device="cuda"):
+    """Encoded JPEGs -> list of uint8 (rows, cols, 3) device tensors (views of one buffer), PIL's ``convert("RGB")`` bits."""
+    coef, plans, infos, offs, end = jpeg_entropy_batch(datas, windows)
+    out = jpeg_decode(coef.to(device), plans, torch.empty(end, dtype=torch.uint8, device=device))
+    res = []
+    for i, (info, off) in enumerate(zip(infos, offs)):
+        rows, cols = (info.height, info.width) if windows is None or windows[i] is None else windows[i][2:]
+        res.append(out[off:off + rows * cols * 3].view(rows, cols, 3))
+    return res
+
+
 def dinoaug_plan_bytes():
     return _lib.load().vtx_dinoaug_plan_bytes()
 
