@@ -573,7 +573,8 @@ int vtx_resized_crop(const void* buf, size_t buf_bytes, const void* table, void*
 /* ---- Baseline JPEG decode, the first stage of the input pipeline (csrc/jpeg_host.h + csrc/jpeg.hip; SURVEY section 8 row F4;
  * reference dataset.py:144, Image.open(buffer).convert("RGB")): bit-exact to PIL's decoder, i.e. libjpeg's default integer path
  * (JDCT_ISLOW, fancy upsampling, table-driven YCbCr -> RGB).  The Huffman bit stream is decoded on the HOST into de-zigzagged
- * int16 coefficient blocks (reentrant, no global state: one call per image from any thread); dequantisation, inverse DCT,
+ * int16 coefficient blocks (reentrant, no global state: one call per image from any thread) -- or, with the entries of the next
+ * section, on the device into the same bytes; dequantisation, inverse DCT,
  * chroma upsampling and colour conversion run on the device, two launches per batch; the pixels land as H x W x 3 uint8 rows in
  * the byte buffer vtx_resized_crop reads.
  * Accepted: SOF0 (or SOF1 with 8-bit tables), 8-bit, one interleaved scan, 1 component or YCbCr with luma sampling (1,1), (2,1)
@@ -607,6 +608,42 @@ int vtx_jpeg_entropy_decode(const void* data, size_t len, const int* window, voi
                             void* plan, int* reason);
 int vtx_jpeg_decode(const void* coef, size_t coef_bytes, const void* plans, int n, void* ws, size_t ws_bytes, void* out,
                     size_t out_bytes, void* stream);
+
+/* ---- The entropy (Huffman) stage on the device (csrc/jpeg_sync.h + csrc/jpeg_entropy.hip; DESIGN.md "Entropy stage on the
+ * device"): an alternative to vtx_jpeg_entropy_decode that leaves only the header parse and a byte scan on the host.  The
+ * coefficient buffer is device memory: it has the same bytes vtx_jpeg_entropy_decode writes and vtx_jpeg_decode reads it as before.
+ *   scan record (vtx_jpeg_scan_bytes() = 8640 bytes, csrc/jpeg_sync.h JsScan): geometry, the stored rectangle, the restart
+ *     interval, offsets, and the DC / AC Huffman table of each component.
+ *   segment table: 16 bytes per restart interval (one for a file without markers): where the interval's bytes lie and how many
+ *     blocks it holds.  stream: the entropy-coded bytes with the stuffed zero bytes and the markers removed.
+ * vtx_jpeg_scan_prepare (host, reentrant): offs = {coefficient, plane, output, stream, segment table} byte offsets and the index
+ *   of the image's first subsequence; writes the plan record of vtx_jpeg_entropy_decode, the scan record, the segment table at
+ *   segs + offs[4] and the bytes at stream + offs[3].  Same reason codes as vtx_jpeg_entropy_decode for every header refusal and
+ *   for a restart marker that is missing or out of sequence (13); 15 also for a scan of 2^28 bytes or more.  Bad codes and
+ *   truncated data are found by the decode.
+ * vtx_jpeg_scan_stream_bytes / _segment_bytes / _subsequences: upper bounds of what prepare writes for one file (0 for what it
+ *   refuses); vtx_jpeg_entropy_workspace_bytes(n, segment bytes, subsequences): the workspace of a batch, 16-byte aligned.
+ * vtx_jpeg_entropy_launch: stream_dev = the DEVICE copy of the bytes; segs / scans = HOST tables, every record and segment
+ *   checked against stream_bytes, seg_bytes, coef_bytes and ws_bytes before anything is launched (VTX_ERR_JPEG), then copied to
+ *   the head of ws on `stream`; coef / status: device.  One launch, one workgroup per image, no synchronisation, no allocation.
+ *   status[i] = 0, 13 (corrupt or truncated entropy-coded data: exactly where vtx_jpeg_entropy_decode says 13) or 100 (not
+ *   converged within `cap` rounds, cap <= 0 meaning vtx_jpeg_round_cap(): decode that file with vtx_jpeg_entropy_decode).  Every block of an image's
+ *   coefficient range is written whatever the status; nothing outside it is.
+ * vtx_jpeg_entropy_emulate: the same arguments in HOST memory, the kernel's algorithm with its lanes as a sequential loop;
+ *   rounds[i] (may be NULL) = rounds run; cap <= 0: vtx_jpeg_round_cap(). */
+size_t vtx_jpeg_scan_bytes(void);
+size_t vtx_jpeg_scan_stream_bytes(const void* data, size_t len);
+size_t vtx_jpeg_scan_segment_bytes(const void* info);
+size_t vtx_jpeg_scan_subsequences(const void* info, size_t stream_bytes);
+size_t vtx_jpeg_entropy_workspace_bytes(int n, size_t seg_bytes, size_t nsub);
+int vtx_jpeg_round_cap(void);
+int vtx_jpeg_subsequence_bits(void);
+int vtx_jpeg_scan_prepare(const void* data, size_t len, const int* window, const long long* offs, void* stream, size_t stream_cap,
+                          void* segs, size_t seg_cap, void* scan, void* plan, int* reason);
+int vtx_jpeg_entropy_launch(const void* stream_dev, size_t stream_bytes, const void* segs, size_t seg_bytes, const void* scans, int n,
+                            void* coef, size_t coef_bytes, void* ws, size_t ws_bytes, int* status, int cap, void* stream);
+int vtx_jpeg_entropy_emulate(const void* stream_host, size_t stream_bytes, const void* segs, size_t seg_bytes, const void* scans, int n,
+                             void* coef, size_t coef_bytes, void* ws, size_t ws_bytes, int* status, int* rounds, int cap);
 
 /* ---- DINOAugment after the crop, on the device (csrc/dinoaug.hip; reference
  * transforms.py:225-294): RandomApply(ColorJitter) -> RandomGrayscale -> GaussianBlur -> Solarize per crop, one launch,

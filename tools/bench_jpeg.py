@@ -5,8 +5,11 @@
   (b) the host entropy stage (csrc/jpeg_host.h) on one core, and (c) on the default pool of 8 threads;
   (d) the two device launches (csrc/jpeg.hip), coefficients already on the device;
   (e) coefficient bytes against decoded bytes;
-  (f) DeviceMixPipeline(crop=...) end to end, from bytes and from decoded arrays.
-Writes the lines, with the commit, to --out (default profiles/jpeg_microbench.txt)."""
+  (f) DeviceMixPipeline(crop=...) end to end, from bytes (host entropy stage, and entropy="device") and from decoded arrays;
+  (g) the host part of the device entropy stage (headers, byte scan, copy) on one core and on the pool of 8;
+  (h) the device entropy launch (csrc/jpeg_entropy.hip), bytes already on the device;
+  (i) rounds per image of the self-synchronising decode (host emulation), mean and maximum.
+Appends the lines, with the commit, to --out (default profiles/jpeg_microbench.txt)."""
 import argparse
 import io
 import os
@@ -99,8 +102,10 @@ def main():
                  f"({coef.numel() / end:.2f} x); encoded {sum(map(len, datas)) / 1e6:.1f} MB")
     arrays = [np.asarray(Image.open(io.BytesIO(d)).convert("RGB")) for d in datas]
     labels = torch.arange(n, device=dev)
-    for name, images in (("bytes", datas), ("arrays", arrays)):
-        pipe = DeviceMixPipeline(crop=RandomResizedCropPlan(224, generator=torch.Generator().manual_seed(0)), seed=0)
+    for name, images, entropy, mode in (("bytes", datas, "host", "late"), ("bytes", datas, "device", "late"),
+                                        ("bytes", datas, "device", "wait"), ("arrays", arrays, "host", "late")):
+        pipe = DeviceMixPipeline(crop=RandomResizedCropPlan(224, generator=torch.Generator().manual_seed(0)), seed=0, entropy=entropy,
+                                 jpeg_status=mode)
         for _ in range(3):
             pipe(images, labels)
         torch.cuda.synchronize()
@@ -110,12 +115,38 @@ def main():
             torch.cuda.synchronize()
 
         t = wall_ms(call, 5)
-        lines.append(f"(f) DeviceMixPipeline(crop=224) from {name:6s}: {t:8.2f} ms per batch wall = {n / t * 1e3:7.0f} images/s; "
-                     f"upload {pipe.upload_bytes / 1e6:.1f} MB")
+
+        def host_only():                                # what the caller's thread spends in the call: no wait for the device
+            pipe(images, labels)
+
+        th = wall_ms(host_only, 5)
+        torch.cuda.synchronize()
+        tag = f"from {name:6s}" if entropy == "host" else f'entropy="device", jpeg_status="{mode}"'
+        lines.append(f"(f) DeviceMixPipeline(crop=224) {tag}: {t:8.2f} ms per batch wall = {n / t * 1e3:7.0f} images/s; "
+                     f"host thread {th:6.2f} ms per call; upload {pipe.upload_bytes / 1e6:.1f} MB" + (f"; host fallbacks {pipe.jpeg_fallbacks}" if entropy == "device" else ""))
+    one = wall_ms(lambda: ops.jpeg_scan_prepare_batch(datas), 3)
+    many = wall_ms(lambda: ops.jpeg_scan_prepare_batch(datas, pool=pool), 3)
+    lines.append(f"(g) host prepare for the device entropy stage: one core {one:8.2f} ms per batch = {n / one * 1e3:7.0f} images/s "
+                 f"({one / n * 1e3:.1f} us per image); pool of 8 {many:8.2f} ms = {n / many * 1e3:7.0f} images/s")
+    pin = lambda kind, nbytes: torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+    batch = ops.jpeg_scan_prepare_batch(datas, alloc=pin)
+    dstream = batch.stream.to(dev)
+    dcoef2, status = ops.jpeg_entropy_device(batch, dstream)
+    _, nws = ops._jpeg_entropy_ws(batch)
+    ws = torch.empty(nws // 8 + 2, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()
+    assert torch.equal(dcoef2, dcoef), "device entropy stage differs from the host stage"
+    g = min(gpu_ms(lambda: ops.jpeg_entropy_device(batch, dstream, dcoef2, ws, status), 10) for _ in range(3))
+    lines.append(f"(h) device entropy launch (S = {ops._lib.load().vtx_jpeg_subsequence_bits()} bits, cap {ops.jpeg_round_cap()} rounds): "
+                 f"{g:8.3f} ms per batch = {n / g * 1e3:7.0f} images/s of GPU time; statuses {sorted(set(status.tolist()))}; "
+                 f"upload {batch.upload_bytes / 1e6:.1f} MB")
+    _, _, rounds = ops.jpeg_entropy_emulate(batch)
+    lines.append(f"(i) rounds per image (host emulation): mean {np.mean(rounds):.2f}, max {max(rounds)}; subsequences per image "
+                 f"{batch.scans.numpy().reshape(n, -1)[:, 44:48].copy().view('<i4').mean():.0f}")
     text = "\n".join(lines) + "\n"
     print(text, end="")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
+    with open(args.out, "a") as fh:                   # appended: the earlier commits' blocks stay on record
         fh.write(text)
 
 

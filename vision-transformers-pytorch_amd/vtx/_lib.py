@@ -220,6 +220,19 @@ _SIGNATURES = {
     "vtx_jpeg_workspace_bytes": (c_size_t, [c_int, c_size_t]),
     "vtx_jpeg_entropy_decode": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "vtx_jpeg_decode": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "vtx_jpeg_scan_bytes": (c_size_t, []),
+    "vtx_jpeg_scan_stream_bytes": (c_size_t, [c_void_p, c_size_t]),
+    "vtx_jpeg_scan_segment_bytes": (c_size_t, [c_void_p]),
+    "vtx_jpeg_scan_subsequences": (c_size_t, [c_void_p, c_size_t]),
+    "vtx_jpeg_entropy_workspace_bytes": (c_size_t, [c_int, c_size_t, c_size_t]),
+    "vtx_jpeg_round_cap": (c_int, []),
+    "vtx_jpeg_subsequence_bits": (c_int, []),
+    "vtx_jpeg_scan_prepare": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
+                                      c_void_p, c_void_p]),
+    "vtx_jpeg_entropy_launch": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_size_t, c_void_p,
+                                        c_size_t, c_void_p, c_int, c_void_p]),
+    "vtx_jpeg_entropy_emulate": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_size_t, c_void_p,
+                                         c_size_t, c_void_p, c_void_p, c_int]),
     "vtx_dinoaug_plan_bytes": (c_size_t, []),
     "vtx_dinoaug_max_box_radius": (c_int, []),
     "vtx_dinoaug_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),

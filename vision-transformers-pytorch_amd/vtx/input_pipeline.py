@@ -23,6 +23,13 @@ into coefficient blocks on a thread pool (csrc/jpeg_host.h; ``decode_threads``, 
 bounding rectangle of its crops needs are uploaded, and the device decodes them (csrc/jpeg.hip: dequantisation, inverse DCT,
 chroma upsampling, colour conversion, bit-exact to PIL's decoder) straight into the byte buffer the resample reads.  A file the
 decoder refuses (progressive, CMYK, ...) raises VtxError before anything is launched: decode it with PIL and pass the array.
+With ``entropy="device"`` (every pipeline with a crop stage takes it; the default is "host") the Huffman streams are decoded on
+the device too (csrc/jpeg_entropy.hip): the host parses the headers and copies the entropy-coded bytes, what is uploaded is those
+bytes plus the tables (``upload_bytes`` counts exactly that), and the coefficient blocks never cross PCIe.  Corrupt or truncated
+entropy-coded data is then found by the device: the status is examined at the start of the next call, or by
+``check_jpeg_status()``, and raises VtxError naming the batch and the file; so does a file whose decode did not converge within
+the round cap.  ``jpeg_status="wait"`` reads the status inside the call instead (the host waits for the entropy kernel), sends a
+file that did not converge through the host stage and raises for a corrupt one at once.
 ``DeviceEvalPipeline`` is the validation transform (Resize + CenterCrop + ToTensor + Normalize, factory.py:215-222) and
 ``DeviceMultiCrop`` the crop stage of DINOAugment (transforms.py:249-279) on the same kernel.
 
@@ -511,12 +518,78 @@ class _CropStage(_UploadRing):
     """The crop stage the pipelines share: validate, pack and upload the pixels the crops read, launch the resample.
     ``crop_records`` holds the records of the last call (boxes, flips), ``upload_bytes`` the size of its upload."""
 
-    def __init__(self, decode_threads=8):
+    def __init__(self, decode_threads=8, entropy="host", jpeg_status="late"):
         super().__init__()
         if not 1 <= int(decode_threads) <= MAX_DECODE_THREADS:
             raise ValueError(f"decode_threads {decode_threads} outside 1..{MAX_DECODE_THREADS}")
-        self.decode_threads, self._pool = int(decode_threads), None
+        if entropy not in ("host", "device"):
+            raise ValueError(f"entropy {entropy!r}: 'host' or 'device'")
+        if jpeg_status not in ("late", "wait"):
+            raise ValueError(f"jpeg_status {jpeg_status!r}: 'late' or 'wait'")
+        self.decode_threads, self._pool, self.entropy, self.jpeg_status = int(decode_threads), None, entropy, jpeg_status
         self.crop_records, self.upload_bytes = [], 0
+        self.jpeg_batches, self.jpeg_fallbacks, self._jpeg_pending = 0, 0, None
+        self._jpeg_cap = 0                        # round cap of the device entropy stage, 0 = the library's (tests lower it)
+
+    def check_jpeg_status(self):
+        """entropy="device": examine the status the device wrote for the last batch of encoded files (it was copied to pinned
+        memory behind an event; by the next call that copy has long finished).  Raises VtxError for a file whose entropy-coded
+        data is corrupt or truncated, or whose decode did not converge within the round cap, naming the batch and the file's
+        index among ``images``; the crops of that file in that batch are not valid.  Called at the start of every call; call
+        it yourself after the last batch."""
+        pending, self._jpeg_pending = self._jpeg_pending, None
+        if pending is None:
+            return
+        batch_no, status, ev, sources = pending
+        ev.synchronize()
+        err = ops.jpeg_status_error(status.tolist(), batch_no, sources)
+        if err is not None:
+            raise err
+
+    def _entropy_on_device(self, images, enc, placed, host, slots, alloc, dev):
+        """upload_crops for entropy="device": what goes up is the entropy-coded bytes, the segment tables and the scan records;
+        the coefficient buffer is device memory written by csrc/jpeg_entropy.hip and read by vtx_jpeg_decode on the same stream."""
+        datas = [images[s].data for s in enc]
+        # on the calling thread: at 15 us per 78 KiB file the pool's hand-over costs more than the work (1.9 ms against 6.1 ms
+        # per 128 files, profiles/jpeg_microbench.txt line (g))
+        batch = ops.jpeg_scan_prepare_batch(datas, [placed[s][1:] for s in enc], lambda kind, nbytes: alloc(nbytes, kind),
+                                            host.numel(), None)
+        if batch.out_offs != [placed[s][0] for s in enc]:
+            raise ops.VtxError("vtx: the decoder's output offsets do not match the packed layout of the sources")
+        n = len(enc)
+        buf = torch.empty(batch.out_end, dtype=torch.uint8, device=dev)
+        if host.numel():
+            buf[:host.numel()].copy_(host, non_blocking=True)
+        slots["images"][1].record()
+        dstream = batch.stream.to(dev, non_blocking=True)
+        slots["jstream"][1].record()
+        coef, status = ops.jpeg_entropy_device(batch, dstream, cap=self._jpeg_cap)
+        slots["jsegs"][1].record()
+        slots["jscans"][1].record()
+        st_host, st_ev = self._pinned(n, torch.int32, "jstatus")
+        st_host[:n].copy_(status, non_blocking=True)
+        st_ev.record()
+        ops.jpeg_decode(coef, batch.plans, buf)
+        self.jpeg_batches += 1
+        slots["jplans"][1].record()
+        self._jpeg_pending = (self.jpeg_batches, st_host[:n], st_ev, list(enc))
+        # jpeg_status="late" (the default): nothing is read here; the next call, or check_jpeg_status(), raises for a corrupt file
+        # and for one that did not converge.  "wait": the status is read inside the call -- the wait is for an event recorded
+        # before the launches above were queued behind it -- a file that did not converge goes through the host stage and the
+        # batch is decoded again, and a corrupt file raises at once.  A file can reach the round cap only when one of its
+        # segments has at least that many subsequences, so a batch without such a file is not waited for.
+        if self.jpeg_status == "wait" and batch.may_not_converge:
+            st_ev.synchronize()
+            redo = [i for i, st in enumerate(st_host[:n].tolist()) if st == ops.JPEG_NOT_CONVERGED]
+            if redo:
+                ops.jpeg_host_fallback(batch, datas, redo, coef)
+                st_host[:n][redo] = 0
+                ops.jpeg_decode(coef, batch.plans, buf)
+                slots["jplans"][1].record()
+                self.jpeg_fallbacks += len(redo)
+            self.check_jpeg_status()
+        self.upload_bytes = host.numel() + batch.upload_bytes
+        return buf, placed
 
     def upload_crops(self, images, records, dev):
         """Validate the records, pack the pixels they read straight into a pinned staging buffer, one asynchronous upload
@@ -526,6 +599,7 @@ class _CropStage(_UploadRing):
         Huffman streams are decoded on the thread pool into a pinned coefficient buffer (only the blocks the window needs),
         that is uploaded instead of pixels and the device decoder writes the windows behind the decoded sources' pixels in
         the same device buffer."""
+        self.check_jpeg_status()
         for rec in records:
             h, w = images[rec["source"]].shape[:2]
             check_crop_record(rec, h, w, rec["out_hw"])
@@ -545,8 +619,10 @@ class _CropStage(_UploadRing):
         # The pool lives as long as the pipeline (its idle threads end with the interpreter).  When one file is refused the
         # exception leaves pool.map while the batch's other jobs may still be writing their blocks: they write into the
         # staging slot their closure keeps alive, and the slot's event is recorded only by a call that launches.
-        if self._pool is None and self.decode_threads > 1:
+        if self._pool is None and self.decode_threads > 1 and self.entropy == "host":
             self._pool = ThreadPoolExecutor(max_workers=self.decode_threads, thread_name_prefix="vtx-jpeg")
+        if self.entropy == "device":
+            return self._entropy_on_device(images, enc, placed, host, slots, alloc, dev)
         coef, plans, _, offs, end = ops.jpeg_entropy_batch([images[s].data for s in enc], [placed[s][1:] for s in enc],
                                                            lambda kind, nbytes: alloc(nbytes, kind), host.numel(), self._pool)
         if offs != [placed[s][0] for s in enc]:
@@ -612,7 +688,7 @@ class DeviceMixPipeline(_CropStage):
     crops of a batch are drawn first, image by image (``boxes`` = [(top, left, h, w, flip)] overrides the draws)."""
 
     def __init__(self, mixup=0.2, cutmix=1, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), erase=None, seed=None,
-                 output="nchw_fp32", randaug=None, mix_before_aug=True, crop=None, decode_threads=8):
+                 output="nchw_fp32", randaug=None, mix_before_aug=True, crop=None, decode_threads=8, entropy="host", jpeg_status="late"):
         if output not in ("nchw_fp32", "nhwc_bf16"):
             raise ValueError(output)
         if randaug is not None and not mix_before_aug:
@@ -622,7 +698,7 @@ class DeviceMixPipeline(_CropStage):
         self.randaug, self.crop = randaug, crop
         self.mean, self.std = torch.tensor(mean, dtype=torch.float32), torch.tensor(std, dtype=torch.float32)
         self.rng = _random.Random(seed) if seed is not None else _random
-        super().__init__(decode_threads)
+        super().__init__(decode_threads, entropy, jpeg_status)
 
     def pack(self, plans):
         """-> (plan table uint8 [N * vtx_mix_plan_bytes()], fill table fp32 or None)"""
@@ -681,10 +757,10 @@ class DeviceEvalPipeline(_CropStage):
     JPEGs (bytes, decoded on the device) -> the normalised batch, ``output`` as in DeviceMixPipeline."""
 
     def __init__(self, valid_size, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), output="nchw_fp32", resize=None,
-                 device="cuda", decode_threads=8):
+                 device="cuda", decode_threads=8, entropy="host", jpeg_status="late"):
         if output not in ("nchw_fp32", "nhwc_bf16"):
             raise ValueError(output)
-        super().__init__(decode_threads)
+        super().__init__(decode_threads, entropy, jpeg_status)
         self.plan, self.output, self.device = CenterCropPlan(valid_size, resize), output, torch.device(device)
         self.mean, self.std = torch.tensor(mean, dtype=torch.float32), torch.tensor(std, dtype=torch.float32)
         self._tables = {}                         # the trivial normalise plan per batch size, on the device
@@ -707,8 +783,8 @@ class DeviceMultiCrop(_CropStage):
     uploaded and decoded on the device).  The draws run image by image, crop by crop.  DINOAugment's flip / ColorJitter / grayscale /
     GaussianBlur / solarize after the crop are ``DeviceDinoAugment``'s."""
 
-    def __init__(self, plans, device="cuda", decode_threads=8):
-        super().__init__(decode_threads)
+    def __init__(self, plans, device="cuda", decode_threads=8, entropy="host", jpeg_status="late"):
+        super().__init__(decode_threads, entropy, jpeg_status)
         self.plans, self.device = list(plans), torch.device(device)
 
     def __call__(self, images, boxes=None):
@@ -847,10 +923,10 @@ class DeviceDinoAugment(_CropStage):
 
     def __init__(self, global_crop_size, local_crop_size, global_crop_scale, local_crop_scale, n_local_crop,
                  mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), output="nchw_fp32", generator=None, rng=None, seed=None,
-                 device="cuda", decode_threads=8):
+                 device="cuda", decode_threads=8, entropy="host", jpeg_status="late"):
         if output not in ("nchw_fp32", "nhwc_bf16"):
             raise ValueError(output)
-        super().__init__(decode_threads)
+        super().__init__(decode_threads, entropy, jpeg_status)
         if rng is None and seed is not None:
             rng = _random.Random(seed)
         self.plan = DinoAugmentPlan(global_crop_size, local_crop_size, global_crop_scale, local_crop_scale, n_local_crop,

@@ -1289,10 +1289,169 @@ def jpeg_decode(coef, plans, out=None):
     return out
 
 
-def jpeg_decode_images(datas, windows=None, device="cuda"):
-    """Encoded JPEGs -> list of uint8 (rows, cols, 3) device tensors (views of one buffer), PIL's ``convert("RGB")`` bits."""
-    coef, plans, infos, offs, end = jpeg_entropy_batch(datas, windows)
-    out = jpeg_decode(coef.to(device), plans, torch.empty(end, dtype=torch.uint8, device=device))
+JPEG_NOT_CONVERGED = 100       # device entropy status: the round cap was reached; the host stage decodes that file
+
+
+class JpegScanBatch:
+    """What ``jpeg_scan_prepare_batch`` hands to ``jpeg_entropy_device`` / ``jpeg_entropy_emulate``: the host tables of a batch
+    (``stream`` = the entropy-coded bytes, ``segs``, ``scans``, ``plans``: uint8 host tensors), the sizes of the device buffers
+    (``coef_bytes``, ``nsub``), and per image ``infos``, ``coef_offs`` and ``out_offs``; ``out_end`` = the end of the pixels."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def upload_bytes(self):
+        """What crosses to the device: the staged stream (each file's room is its entropy-coded bytes as they are in the file,
+        rounded up to 16: a few bytes more than the unstuffed bytes prepare writes), the segment tables and the scan records
+        (the plan table is counted by nobody: ``jpeg_decode`` copies it on both paths)."""
+        return self.stream.numel() + self.segs.numel() + self.scans.numel()
+
+
+def jpeg_scan_bytes():
+    return _lib.load().vtx_jpeg_scan_bytes()
+
+
+def jpeg_round_cap():
+    return _lib.load().vtx_jpeg_round_cap()
+
+
+def jpeg_scan_prepare_batch(datas, windows=None, alloc=None, out_base=0, pool=None):
+    """The host part of the device entropy stage for a batch: headers, layout, then per file (through ``pool.map`` when a thread
+    pool is given) the plan record, the scan record, the segment table and the entropy-coded bytes without their stuffed zeros
+    and markers.  ``alloc(kind, nbytes)`` -> host uint8 tensor for kind "jstream" / "jsegs" / "jscans" / "jplans" (pinned
+    staging memory; default fresh tensors).  Raises VtxError for a refused file, a restart marker out of sequence included.
+    -> JpegScanBatch"""
+    lib = _lib.load()
+    n = len(datas)
+    windows = [None] * n if windows is None else windows
+    infos = [jpeg_info(d) for d in datas]
+    pb, sb = jpeg_plan_bytes(), jpeg_scan_bytes()
+    offs, co, po, oo, so, go, no = [], 0, 0, int(out_base), 0, 0, 0
+    for d, info, win in zip(datas, infos, windows):
+        cb = jpeg_coef_bytes(info, win)
+        if cb == 0:
+            raise VtxError(f"vtx: JPEG decode window {win} outside the {info.height} x {info.width} image, or more than 2^26 blocks "
+                           f"/ 2^28 pixels to store (nothing is allocated for such a file)")
+        nstream = lib.vtx_jpeg_scan_stream_bytes(_jpeg_ptr(d), len(d))
+        nseg = lib.vtx_jpeg_scan_segment_bytes(ctypes.byref(info))
+        nsub = lib.vtx_jpeg_scan_subsequences(ctypes.byref(info), nstream)
+        if nstream == 0 or nseg == 0 or nsub == 0:
+            raise VtxError("vtx: an entropy-coded segment of 2^28 bytes or more is not decoded on the device")
+        rows, cols = (info.height, info.width) if win is None else (win[2], win[3])
+        offs.append((co, po, oo, so, go, no))
+        co, po, oo, so, go, no = co + cb, po + cb // 2, oo + rows * cols * 3, so + nstream, go + nseg, no + nsub
+    alloc = alloc or (lambda kind, nbytes: torch.empty(nbytes, dtype=torch.uint8))
+    stream, segs = alloc("jstream", so)[:so], alloc("jsegs", go)[:go]
+    scans, plans = alloc("jscans", n * sb)[:n * sb], alloc("jplans", n * pb)[:n * pb]
+
+    def job(i):
+        reason = ctypes.c_int(0)
+        o = (ctypes.c_longlong * 6)(*offs[i])
+        rc = lib.vtx_jpeg_scan_prepare(_jpeg_ptr(datas[i]), len(datas[i]), _jpeg_window(windows[i]), o, stream.data_ptr(), so,
+                                       segs.data_ptr(), go, scans.data_ptr() + i * sb, plans.data_ptr() + i * pb, ctypes.byref(reason))
+        if rc != 0:
+            raise VtxError(f"vtx_jpeg_scan_prepare: not a supported JPEG: {JPEG_REASONS.get(reason.value, 'bad arguments')} "
+                           f"(code {rc}, reason {reason.value})")
+
+    list(pool.map(job, range(n)) if pool is not None and n > 1 else map(job, range(n)))
+    # a segment of m subsequences is final after m rounds: only a file with a segment of jpeg_round_cap() or more can reach the cap
+    counts = scans.numpy().reshape(n, sb)[:, 40:48].copy().view("<i4")
+    may_not_converge = bool(((counts[:, 1] - counts[:, 0] + 1) >= jpeg_round_cap()).any())
+    return JpegScanBatch(may_not_converge=may_not_converge, stream=stream, segs=segs, scans=scans, plans=plans, infos=infos, windows=windows, coef_bytes=co, nsub=no,
+                         coef_offs=[o[0] for o in offs], offs=offs, out_offs=[o[2] for o in offs], out_end=oo)
+
+
+def _jpeg_entropy_ws(batch):
+    n = batch.scans.numel() // jpeg_scan_bytes()
+    return n, _lib.load().vtx_jpeg_entropy_workspace_bytes(n, batch.segs.numel(), batch.nsub)
+
+
+def jpeg_entropy_device(batch, stream_dev=None, coef=None, ws=None, status=None, device="cuda", cap=0):
+    """The entropy stage on the device (csrc/jpeg_entropy.hip): one launch, one workgroup per image, no synchronisation.
+    ``stream_dev``: the device copy of ``batch.stream`` (default: uploaded here); ``coef`` / ``ws`` / ``status``: device buffers
+    (default fresh ones).  -> (coef uint8 device tensor with the bytes the host stage writes, status int32 device tensor:
+    0, 13 or JPEG_NOT_CONVERGED per image).  Pinned ``segs`` / ``scans`` stay unchanged until the stream has copied them.
+    ``cap``: the round cap, 0 = jpeg_round_cap() (a smaller one is for tests of the fallback)."""
+    lib = _lib.load()
+    n, nws = _jpeg_entropy_ws(batch)
+    if stream_dev is None:
+        stream_dev = batch.stream.to(device, non_blocking=batch.stream.is_pinned())
+    _dev(stream_dev)
+    dev = stream_dev.device
+    coef = torch.empty(max(batch.coef_bytes, 1), dtype=torch.uint8, device=dev) if coef is None else coef
+    ws = torch.empty((nws + 15) // 16 * 2, dtype=torch.int64, device=dev) if ws is None else ws
+    status = torch.empty(n, dtype=torch.int32, device=dev) if status is None else status
+    _dev(coef, ws, status)
+    if status.dtype != torch.int32 or status.numel() < n:
+        raise VtxError("vtx: jpeg_entropy_device writes one int32 status per image")
+    check(lib.vtx_jpeg_entropy_launch(_p(stream_dev), stream_dev.numel(), batch.segs.data_ptr(), batch.segs.numel(), batch.scans.data_ptr(),
+                                      n, _p(coef), coef.numel() * coef.element_size(), _p(ws), ws.numel() * ws.element_size(), _p(status),
+                                      int(cap), _stream()), "vtx_jpeg_entropy_launch")
+    if not (batch.segs.is_pinned() and batch.scans.is_pinned()):
+        torch.cuda.current_stream().synchronize()
+    return coef, status
+
+
+def jpeg_entropy_emulate(batch, cap=0, coef=None):
+    """Host only: the kernel's algorithm with its lanes as a sequential loop (csrc/jpeg_sync.h), bit for bit.
+    -> (coef uint8 host tensor, [status], [rounds run])"""
+    lib = _lib.load()
+    n, nws = _jpeg_entropy_ws(batch)
+    coef = torch.empty(max(batch.coef_bytes, 1), dtype=torch.uint8) if coef is None else coef
+    ws = torch.empty((nws + 15) // 16 * 2, dtype=torch.int64)
+    status, rounds = torch.zeros(n, dtype=torch.int32), torch.zeros(n, dtype=torch.int32)
+    check(lib.vtx_jpeg_entropy_emulate(batch.stream.data_ptr(), batch.stream.numel(), batch.segs.data_ptr(), batch.segs.numel(),
+                                       batch.scans.data_ptr(), n, coef.data_ptr(), coef.numel(), ws.data_ptr(), ws.numel() * 8,
+                                       status.data_ptr(), rounds.data_ptr(), int(cap)), "vtx_jpeg_entropy_emulate")
+    return coef[:batch.coef_bytes], status.tolist(), rounds.tolist()
+
+
+def jpeg_host_fallback(batch, datas, indices, coef_dev):
+    """The files ``indices`` of a batch (the ones the device reported JPEG_NOT_CONVERGED for) through the host entropy stage, their
+    coefficients copied over the device's.  Raises VtxError when the host stage refuses one."""
+    pb = jpeg_plan_bytes()
+    for i in indices:
+        cb = jpeg_coef_bytes(batch.infos[i], batch.windows[i])
+        host = torch.empty(cb, dtype=torch.uint8)
+        jpeg_entropy_decode(datas[i], host, (0, batch.offs[i][1], batch.offs[i][2]), torch.empty(pb, dtype=torch.uint8), batch.windows[i])
+        off = batch.coef_offs[i]
+        coef_dev[off:off + cb].copy_(host)
+
+
+def jpeg_status_error(status, batch_no=None, sources=None):
+    """VtxError for the first file of a device status list that is not 0 (``sources[i]``: its index among the caller's images,
+    ``batch_no``: the pipeline's batch), or None."""
+    for i, st in enumerate(status):
+        if st != 0:
+            k = i if sources is None else sources[i]
+            where = f"file {k}" if batch_no is None else f"file {k} of batch {batch_no}"
+            what = JPEG_REASONS[13] if st == 13 else (f"the decode did not converge within {jpeg_round_cap()} rounds: decode this file "
+                                                      f"with entropy=\"host\"" if st == JPEG_NOT_CONVERGED else f"device status {st}")
+            return VtxError(f"vtx_jpeg_entropy_launch: {where}: not a supported JPEG: {what} (reason {st})")
+    return None
+
+
+def jpeg_decode_images(datas, windows=None, device="cuda", entropy="host"):
+    """Encoded JPEGs -> list of uint8 (rows, cols, 3) device tensors (views of one buffer), PIL's ``convert("RGB")`` bits.
+    ``entropy``: "host" (the Huffman streams on the host, the default) or "device" (csrc/jpeg_entropy.hip; this convenience
+    entry reads the status back, sends a file that did not converge through the host stage and raises for a corrupt one)."""
+    if entropy not in ("host", "device"):
+        raise ValueError(entropy)
+    if entropy == "device":
+        batch = jpeg_scan_prepare_batch(datas, windows)
+        coef, status = jpeg_entropy_device(batch, device=device)
+        status = status.tolist()
+        redo = [i for i, s in enumerate(status) if s == JPEG_NOT_CONVERGED]
+        err = jpeg_status_error([0 if s == JPEG_NOT_CONVERGED else s for s in status])
+        if err is not None:
+            raise err
+        jpeg_host_fallback(batch, datas, redo, coef)
+        plans, infos, offs, end = batch.plans, batch.infos, batch.out_offs, batch.out_end
+        out = jpeg_decode(coef, plans, torch.empty(end, dtype=torch.uint8, device=device))
+    else:
+        coef, plans, infos, offs, end = jpeg_entropy_batch(datas, windows)
+        out = jpeg_decode(coef.to(device), plans, torch.empty(end, dtype=torch.uint8, device=device))
     res = []
     for i, (info, off) in enumerate(zip(infos, offs)):
         rows, cols = (info.height, info.width) if windows is None or windows[i] is None else windows[i][2:]
