@@ -570,6 +570,19 @@ int vtx_resample_coeffs(int L, int S, int first, int n, void* table, void* strea
 int vtx_resized_crop(const void* buf, size_t buf_bytes, const void* table, void* ws, size_t ws_bytes, void* out, int M, int S_h,
                      int S_w, void* stream);
 
+/* Down-scales beyond 16, opt-in (vtx.input_pipeline: max_downscale): a second launch over the records of the SAME table that
+ * vtx_resized_crop zero-filled because a side has more than 65 taps.  idx = device int32[L], the indices of those records; only
+ * their images of out ([M, 3, S_h, S_w], the tensor vtx_resized_crop wrote) are written, everything else is left untouched.
+ * max_taps: the size of the coefficient tables, 1..513 (513 = crop side / output side 128; a chosen bound) and at least the
+ * largest tap count among the L records; ws = vtx_resample_long_workspace_bytes(L, S_h, S_w, max_taps) device bytes
+ * = L * (2 + max_taps) * (S_h + S_w) int32 (0 for arguments the entry refuses).  Same arithmetic, bit-exact to PIL: a vertical
+ * window longer than the LDS tile is summed over several tile loads, the int32 accumulators staying in registers.  Argument
+ * violations are VTX_ERR_SHAPE before any launch; a record with more than max_taps taps, outside its source or outside buf is
+ * zero-filled as by vtx_resized_crop; an index outside [0, M) is skipped. */
+size_t vtx_resample_long_workspace_bytes(int L, int S_h, int S_w, int max_taps);
+int vtx_resized_crop_long(const void* buf, size_t buf_bytes, const void* table, const void* idx, int L, int max_taps, void* ws,
+                          size_t ws_bytes, void* out, int M, int S_h, int S_w, void* stream);
+
 /* ---- Baseline JPEG decode, the first stage of the input pipeline (csrc/jpeg_host.h + csrc/jpeg.hip; SURVEY section 8 row F4;
  * reference dataset.py:144, Image.open(buffer).convert("RGB")): bit-exact to PIL's decoder, i.e. libjpeg's default integer path
  * (JDCT_ISLOW, fancy upsampling, table-driven YCbCr -> RGB).  The Huffman bit stream is decoded on the HOST into de-zigzagged
@@ -578,7 +591,9 @@ int vtx_resized_crop(const void* buf, size_t buf_bytes, const void* table, void*
  * chroma upsampling and colour conversion run on the device, two launches per batch; the pixels land as H x W x 3 uint8 rows in
  * the byte buffer vtx_resized_crop reads.
  * Accepted: SOF0 (or SOF1 with 8-bit tables), 8-bit, one interleaved scan, 1 component or YCbCr with luma sampling (1,1), (2,1)
- * or (2,2) and chroma 1x1, restart intervals.  Refused with VTX_ERR_JPEG and a reason (VTX_JPEG_* of csrc/jpeg_host.h):
+ * or (2,2) and chroma 1x1, restart intervals; progressive (SOF2) and multi-scan sequential files only through the opt-in entries
+ * below (vtx_jpeg_info_ex / vtx_jpeg_entropy_decode_ms, reasons 16 and 17).  Refused with VTX_ERR_JPEG and a reason (VTX_JPEG_* of
+ * csrc/jpeg_host.h):
  * 1 not a JPEG / malformed header, 2 progressive, 3 arithmetic, 4 lossless / hierarchical, 5 12-bit samples or 16-bit tables,
  * 6 components other than 1 or 3, 7 other sampling factors, 8 more than one scan, 9 an Adobe transform other than YCbCr,
  * 10 component ids R, G, B without JFIF, 11 DNL, 12 zero dimensions, 13 corrupt or truncated entropy-coded data, 14 a window
@@ -608,6 +623,31 @@ int vtx_jpeg_entropy_decode(const void* data, size_t len, const int* window, voi
                             void* plan, int* reason);
 int vtx_jpeg_decode(const void* coef, size_t coef_bytes, const void* plans, int n, void* ws, size_t ws_bytes, void* out,
                     size_t out_bytes, void* stream);
+
+/* Multi-scan JPEG, opt-in (csrc/jpeg_multiscan.h; vtx.input_pipeline: jpeg_scans="any"): progressive DCT (SOF2) and sequential
+ * files whose scans do not each hold every component, through the HOST stage into the same coefficient blocks and plan record,
+ * so that vtx_jpeg_decode and the device kernels run unchanged.  Every scan up to EOI is walked (DHT / DQT / DRI between scans;
+ * DC and AC, first and refinement scans, interleaved or not, EOB runs and correction bits; restart intervals counted in the
+ * scan's own MCUs).  A refinement needs every block's earlier state: the decode works on the whole image's coefficients in a
+ * caller-owned scratch (zeroed by the call) and copies the window's MCU rectangle out; the library allocates nothing.
+ *   vtx_jpeg_info_ex: flags 0 = vtx_jpeg_info; bit 0 accepts those files and records the kind in info.reserved[0]: 0 single scan,
+ *     1 multi-scan sequential, 2 progressive.  Components, sampling, precision, Adobe and RGB-id rules are vtx_jpeg_info's.
+ *   vtx_jpeg_scratch_bytes(info): 0 for kind 0; all blocks of the padded MCU grid x 128 bytes otherwise; 0 for more than 2^22
+ *     blocks (512 MiB), which vtx_jpeg_entropy_decode_ms refuses with reason 15.
+ *   vtx_jpeg_entropy_decode_ms: vtx_jpeg_entropy_decode's arguments plus the scratch (2-byte aligned; NULL for a kind-0 file, which
+ *     goes through vtx_jpeg_entropy_decode); a scratch too small is reason 14.
+ * Further reasons: 16 an invalid scan script -- Ss > Se, Se > 63, a DC scan with Se != 0, an AC scan of several components,
+ *   Al > 13, Ah that is neither 0 for a coefficient not yet sent nor the Al of that coefficient's previous scan, AC before the
+ *   component's first DC scan, a sequential scan other than Ss = 0, Se = 63, Ah = Al = 0 or a component in two of them, more than
+ *   256 scans (libjpeg's JERR_BAD_PROGRESSION / JERR_BAD_PROG_SCRIPT, and its JWRN_BOGUS_PROGRESSION warning is a refusal here);
+ *   17 an incomplete progression: at EOI coefficients 0..9 of every component must have ended at Al = 0 (libjpeg smooths blocks
+ *   otherwise, differently in different versions), and every component of a sequential file must have had its scan.
+ *   Coefficients above 9 never sent are zero, those left at Al > 0 keep their partial value, as in libjpeg.  Data that ends before
+ *   EOI or inside a scan is reason 13. */
+int vtx_jpeg_info_ex(const void* data, size_t len, void* info, int flags);
+size_t vtx_jpeg_scratch_bytes(const void* info);
+int vtx_jpeg_entropy_decode_ms(const void* data, size_t len, const int* window, void* coef, size_t coef_bytes, const long long* offs,
+                               void* plan, void* scratch, size_t scratch_bytes, int* reason);
 
 /* ---- The entropy (Huffman) stage on the device (csrc/jpeg_sync.h + csrc/jpeg_entropy.hip; DESIGN.md "Entropy stage on the
  * device"): an alternative to vtx_jpeg_entropy_decode that leaves only the header parse and a byte scan on the host.  The

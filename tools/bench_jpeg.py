@@ -9,7 +9,11 @@
   (g) the host part of the device entropy stage (headers, byte scan, copy) on one core and on the pool of 8;
   (h) the device entropy launch (csrc/jpeg_entropy.hip), bytes already on the device;
   (i) rounds per image of the self-synchronising decode (host emulation), mean and maximum.
-Appends the lines, with the commit, to --out (default profiles/jpeg_microbench.txt)."""
+Appends the lines, with the commit, to --out (default profiles/jpeg_microbench.txt).
+
+``--multiscan``: instead, host only, the multi-scan stage (csrc/jpeg_multiscan.h) on PROGRESSIVE re-encodes of the same 128 images:
+  (j) PIL's full decode of the progressive files on one core;
+  (k) the multi-scan host stage (whole images) on one core, and (l) on the pool of 8 threads, with the scratch it keeps per thread."""
 import argparse
 import io
 import os
@@ -28,16 +32,16 @@ import jpeg_np as J
 from vtx import ops
 from vtx.input_pipeline import DeviceMixPipeline, RandomResizedCropPlan
 
-dev = torch.device("cuda")
+dev = torch.device("cuda")                            # (a device object only: --multiscan never touches the GPU)
 
 
-def files(n=128):
+def files(n=128, progressive=False):
     from PIL import Image
     out = []
     for k in range(n):
         h, w = (500 - k % 7, 375 - k % 5) if k % 4 == 1 else (375 - k % 5, 500 - k % 7)
         b = io.BytesIO()
-        Image.fromarray(J.synth(h, w, 900 + k, noise=12)).save(b, "JPEG", quality=90, subsampling=2)
+        Image.fromarray(J.synth(h, w, 900 + k, noise=12)).save(b, "JPEG", quality=90, subsampling=2, progressive=progressive)
         out.append(b.getvalue())
     return out
 
@@ -66,6 +70,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "jpeg_microbench.txt"))
     ap.add_argument("--commit", default=None)
+    ap.add_argument("--multiscan", action="store_true")
     args = ap.parse_args()
     commit = args.commit
     if commit is None:
@@ -74,6 +79,8 @@ def main():
         except OSError:
             commit = ""
     from PIL import Image
+    if args.multiscan:
+        return multiscan(args, commit)
     datas = files()
     n = len(datas)
     lines = [f"JPEG decode micro-benchmark, commit {commit or 'unknown'}: {n} PIL-encoded files of about 500 x 375, quality 90, 4:2:0, "
@@ -147,6 +154,34 @@ def main():
     print(text, end="")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "a") as fh:                   # appended: the earlier commits' blocks stay on record
+        fh.write(text)
+
+
+def multiscan(args, commit):
+    from PIL import Image
+    datas = files(progressive=True)
+    n = len(datas)
+    infos = [ops.jpeg_info(d, scans="any") for d in datas]
+    assert all(i.reserved[0] == 2 for i in infos)
+    lines = [f"Multi-scan JPEG host stage, commit {commit or 'unknown'}: {n} PIL-encoded PROGRESSIVE files (10 scans) of about 500 x 375, "
+             f"quality 90, 4:2:0, {sum(map(len, datas)) / n / 1024:.1f} KiB each; host only, {os.cpu_count()} CPUs visible"]
+
+    def pil_all():
+        for d in datas:
+            np.asarray(Image.open(io.BytesIO(d)).convert("RGB"))
+
+    pil = wall_ms(pil_all, 2)
+    lines.append(f"(j) PIL full decode of the progressive files, one core: {pil:8.2f} ms per batch = {n / pil * 1e3:7.0f} images/s")
+    one = wall_ms(lambda: ops.jpeg_entropy_batch(datas, scans="any"), 2)
+    lines.append(f"(k) multi-scan host stage, one core:                    {one:8.2f} ms per batch = {n / one * 1e3:7.0f} images/s "
+                 f"({pil / one:.2f} x PIL's full decode" + (": SLOWER than PIL" if one > pil else "") + ")")
+    pool = ThreadPoolExecutor(max_workers=8)
+    many = wall_ms(lambda: ops.jpeg_entropy_batch(datas, pool=pool, scans="any"), 3)
+    lines.append(f"(l) multi-scan host stage, pool of 8 threads:           {many:8.2f} ms per batch = {n / many * 1e3:7.0f} images/s; "
+                 f"scratch {max(ops.jpeg_scratch_bytes(i) for i in infos) / 1e6:.2f} MB per thread")
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    with open(args.out, "a") as fh:
         fh.write(text)
 
 

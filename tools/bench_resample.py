@@ -3,8 +3,13 @@
 500 x 375 (landscape, portrait, some small), RandomResizedCrop(224) + flip.  Reports the GPU time of the resample launches
 alone (events around replays of one packed table), the host time of drawing + packing per batch (into a pinned buffer), the
 bytes uploaded, and the copy rate the box delivers for the kernel's bytes; with Pillow installed also PIL's time for the
-same crops on one CPU core."""
+same crops on one CPU core.
+
+``--long [--out FILE] [--commit ID]``: instead, the down-scales beyond 16 (vtx_resized_crop_long): GPU time per record of 4 crops
+to 224 x 224 at crop side / output side 17, 32, 64 and 128 on both axes, against the classic launch's time per record at ratio
+16 on the same box; one run, appended with the commit to --out (default profiles/resample_long_microbench.txt)."""
 import os
+import subprocess
 import sys
 import time
 
@@ -42,6 +47,47 @@ def batch(n, seed=2):
         out.append(rng.integers(0, 256, (h, w, 3), dtype=np.uint8))
     return out
 
+
+def long_bench(argv):
+    out = argv[argv.index("--out") + 1] if "--out" in argv else os.path.join(REPO, "profiles", "resample_long_microbench.txt")
+    if "--commit" in argv:
+        commit = argv[argv.index("--commit") + 1]
+    else:
+        try:
+            commit = subprocess.run(["git", "-C", REPO, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
+        except OSError:
+            commit = ""
+    lines = [f"Long resample micro-benchmark, commit {commit or 'unknown'}: 4 crops of one device-resident noise source to 224 x 224 per "
+             f"ratio (crop side / output side on both axes), GPU time of coefficients + resample; {torch.cuda.get_device_name(0)}"]
+    plan = RandomResizedCropPlan(224)
+    base = None
+    for ratio in (16, 17, 32, 64, 128):
+        side = 224 * ratio
+        h = w = side + 8
+        src = torch.randint(0, 256, (h * w * 3,), dtype=torch.uint8, device=dev)
+        recs = [plan.record(h, w, (t, l, side, side, bool(k & 1)), source=0) for k, (t, l) in enumerate(((0, 0), (8, 3), (2, 8), (5, 5)))]
+        table = pack_crop_table(recs, {0: (0, 0, 0, h, w)}).to(dev)
+        taps = 4 * ratio + 1
+        far = list(range(4)) if ratio > 16 else []
+        fn = lambda: ops.resized_crop(src, table, 224, max_taps=max(taps, 65), long_records=far)
+        fn()
+        torch.cuda.synchronize()
+        ms = gpu_ms(fn, 5 if ratio <= 32 else 2) / 4
+        if ratio == 16:
+            base = ms
+            lines.append(f"ratio  16 ( 65 taps), classic launch: {ms * 1e3:10.1f} us per record")
+        else:                                             # the classic launch still runs (and zero-fills) in front of the long one
+            lines.append(f"ratio {ratio:3d} ({taps:3d} taps), classic + long launch: {ms * 1e3:10.1f} us per record = {ms / base:6.1f} x "
+                         f"ratio 16 ({(ratio / 16) ** 2:5.1f} x the source pixels)")
+        del src
+    print("\n".join(lines))
+    with open(out, "a") as fh:                             # appended: earlier commits' blocks stay on record
+        fh.write("\n".join(lines) + "\n")
+
+
+if "--long" in sys.argv:
+    long_bench(sys.argv)
+    sys.exit(0)
 
 n = 128
 images = batch(n)

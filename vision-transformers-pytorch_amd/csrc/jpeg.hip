@@ -13,6 +13,7 @@
 // geometry, none from image data.
 #include "vtx_common.h"
 #include "jpeg_host.h"
+#include "jpeg_multiscan.h"
 
 #define JPEG_THREADS 256
 #define JPEG_HEAD_ALIGN 256
@@ -182,6 +183,29 @@ int vtx_jpeg_entropy_decode(const void* data, size_t len, const int* window, voi
  * head of the workspace on `stream`: when it is pinned memory the caller keeps it unchanged until the stream has passed the copy);
  * ws: vtx_jpeg_workspace_bytes(n, plane bytes) device bytes, 8-byte aligned; out: device bytes, each image's window as rows x cols
  * x 3 at its out_off.  Any record outside the sizes given: VTX_ERR_JPEG, nothing launched. */
+/* Multi-scan files, opt-in (csrc/jpeg_multiscan.h), host only and reentrant.  vtx_jpeg_info_ex: flags 0 = vtx_jpeg_info; bit 0
+ * accepts SOF2 and sequential files whose scans do not each hold every component, and records the kind in info->reserved[0]
+ * (0 single scan, 1 multi-scan sequential, 2 progressive).  vtx_jpeg_scratch_bytes: the whole-image scratch of such a file (0
+ * for kind 0 and for more than 2^22 blocks).  vtx_jpeg_entropy_decode_ms: vtx_jpeg_entropy_decode for a file of any kind. */
+int vtx_jpeg_info_ex(const void* data, size_t len, void* info, int flags) {
+  if (!data || !info) return VTX_ERR_NULL;
+  VtxJpegInfo in;
+  const int rc = jpeg_info_ex((const unsigned char*)data, len, &in, flags);
+  memcpy(info, &in, sizeof(VtxJpegInfo));
+  return rc ? VTX_ERR_JPEG : VTX_OK;
+}
+
+size_t vtx_jpeg_scratch_bytes(const void* info) { return jpeg_scratch_bytes_of((const VtxJpegInfo*)info); }
+
+int vtx_jpeg_entropy_decode_ms(const void* data, size_t len, const int* window, void* coef, size_t coef_bytes, const long long* offs,
+                               void* plan, void* scratch, size_t scratch_bytes, int* reason) {
+  if (!data || !coef || !offs || !plan) return VTX_ERR_NULL;
+  const int rc = jpeg_entropy_decode_ms((const unsigned char*)data, len, window, coef, coef_bytes, offs, (VtxJpegPlan*)plan, scratch,
+                                        scratch_bytes);
+  if (reason) *reason = rc;
+  return rc ? VTX_ERR_JPEG : VTX_OK;
+}
+
 int vtx_jpeg_decode(const void* coef, size_t coef_bytes, const void* plans, int n, void* ws, size_t ws_bytes, void* out,
                     size_t out_bytes, void* stream) {
   if (!coef || !plans || !ws || !out) return VTX_ERR_NULL;

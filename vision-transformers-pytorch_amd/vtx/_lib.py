@@ -213,6 +213,9 @@ _SIGNATURES = {
     "vtx_resample_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "vtx_resample_coeffs": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vtx_resized_crop": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "vtx_resample_long_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "vtx_resized_crop_long": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_int,
+                                      c_int, c_int, c_void_p]),
     "vtx_jpeg_info": (c_int, [c_void_p, c_size_t, c_void_p]),
     "vtx_jpeg_plan_bytes": (c_size_t, []),
     "vtx_jpeg_coef_bytes": (c_size_t, [c_void_p, c_void_p]),
@@ -220,6 +223,10 @@ _SIGNATURES = {
     "vtx_jpeg_workspace_bytes": (c_size_t, [c_int, c_size_t]),
     "vtx_jpeg_entropy_decode": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "vtx_jpeg_decode": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "vtx_jpeg_info_ex": (c_int, [c_void_p, c_size_t, c_void_p, c_int]),
+    "vtx_jpeg_scratch_bytes": (c_size_t, [c_void_p]),
+    "vtx_jpeg_entropy_decode_ms": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t,
+                                           c_void_p]),
     "vtx_jpeg_scan_bytes": (c_size_t, []),
     "vtx_jpeg_scan_stream_bytes": (c_size_t, [c_void_p, c_size_t]),
     "vtx_jpeg_scan_segment_bytes": (c_size_t, [c_void_p]),

@@ -276,6 +276,7 @@ class RandAugmentPlan:
 
 MAX_DECODE_THREADS = 16                           # entropy-decode pool of the crop stage (never sized by the machine's CPU count)
 MAX_TAPS = 65                                     # = vtx_resample_max_taps(): crop side / output side <= 16
+MAX_DOWNSCALE = 128                               # the largest ``max_downscale`` of the crop stage (513 taps, vtx_resized_crop_long)
 MAX_OUT_WIDTH = 840                               # the LDS tile of csrc/resample.hip holds 65 rows of the output's width
 
 
@@ -375,16 +376,18 @@ class CenterCropPlan:
         return dict(source=source, box=(0, 0, h, w), res=(nh, nw), window=(top, left), flip=False)
 
 
-def check_crop_record(rec, h, w, out_hw):
-    """Raises VtxError for a record outside what csrc/resample.hip computes exactly (it never produces other bits)."""
+def check_crop_record(rec, h, w, out_hw, max_taps=MAX_TAPS):
+    """Raises VtxError for a record outside what csrc/resample.hip computes exactly (it never produces other bits).
+    ``max_taps``: 4 * max_downscale + 1 of a crop stage that opted into down-scales beyond 16."""
     top, left, ch, cw = rec["box"]
     (rh, rw), (wt, wl) = rec["res"], rec["window"]
     if ch < 1 or cw < 1 or top < 0 or left < 0 or top + ch > h or left + cw > w:
         raise ops.VtxError(f"vtx: crop box (top {top}, left {left}, {ch} x {cw}) outside the {h} x {w} image")
     if rh < 1 or rw < 1 or wt < 0 or wl < 0 or wt + out_hw[0] > rh or wl + out_hw[1] > rw:
         raise ops.VtxError(f"vtx: output window {out_hw} at ({wt}, {wl}) outside the resampled {rh} x {rw} image")
-    if resample_taps(ch, rh) > MAX_TAPS or resample_taps(cw, rw) > MAX_TAPS:
-        raise ops.VtxError(f"vtx: crop {ch} x {cw} -> {rh} x {rw}: down-scaling by more than 16 on an axis is not built")
+    if resample_taps(ch, rh) > max_taps or resample_taps(cw, rw) > max_taps:
+        raise ops.VtxError(f"vtx: crop {ch} x {cw} -> {rh} x {rw}: down-scaling by more than {(max_taps - 1) // 4} on an axis is "
+                           f"not built" + (" (max_downscale of the pipeline, up to 128)" if max_taps < 4 * MAX_DOWNSCALE + 1 else ""))
 
 
 def pack_sources(images, records, alloc=None):
@@ -429,20 +432,23 @@ def pack_crop_table(records, placed):
 class EncodedJpeg:
     """An item of ``images`` that came as ``bytes`` / ``bytearray``: an encoded JPEG.  Its header is parsed on the spot (a file
     the decoder refuses raises VtxError here, before anything is launched -- the caller decodes such a file with PIL and
-    passes the array); ``shape`` is what the decoded array's would be."""
+    passes the array); ``shape`` is what the decoded array's would be.  ``scans="any"``: progressive and multi-scan sequential
+    files are accepted too (``info.reserved[0]``: 0 single scan, 1 multi-scan sequential, 2 progressive)."""
 
-    def __init__(self, data):
-        self.data, self.info = data, ops.jpeg_info(data)
+    def __init__(self, data, scans="single"):
+        self.data, self.info = data, ops.jpeg_info(data, scans=scans)
+        if self.info.reserved[0] != 0 and ops.jpeg_scratch_bytes(self.info) == 0:
+            raise ops.VtxError(f"vtx_jpeg_info: not a supported JPEG: {ops.JPEG_REASONS[15]} (reason 15)")
         self.shape = (self.info.height, self.info.width, 3)
 
 
-def _as_images(images):
+def _as_images(images, scans="single"):
     """list of H x W x 3 uint8 host arrays / tensors, or encoded JPEGs as bytes / bytearray -> list of tensors /
     EncodedJpeg; raises for anything else."""
     out = []
     for im in images:
         if isinstance(im, (bytes, bytearray, EncodedJpeg)):
-            out.append(im if isinstance(im, EncodedJpeg) else EncodedJpeg(im))
+            out.append(im if isinstance(im, EncodedJpeg) else EncodedJpeg(im, scans))
             continue
         t = torch.as_tensor(im)
         if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.is_cuda or t.shape[0] < 1 or t.shape[1] < 1:
@@ -518,8 +524,14 @@ class _CropStage(_UploadRing):
     """The crop stage the pipelines share: validate, pack and upload the pixels the crops read, launch the resample.
     ``crop_records`` holds the records of the last call (boxes, flips), ``upload_bytes`` the size of its upload."""
 
-    def __init__(self, decode_threads=8, entropy="host", jpeg_status="late"):
+    def __init__(self, decode_threads=8, entropy="host", jpeg_status="late", max_downscale=16, jpeg_scans="single"):
         super().__init__()
+        if jpeg_scans not in ("single", "any"):
+            raise ValueError(f"jpeg_scans {jpeg_scans!r}: 'single' (the default) or 'any'")
+        self.jpeg_scans = jpeg_scans
+        if isinstance(max_downscale, bool) or not isinstance(max_downscale, int) or not 16 <= max_downscale <= MAX_DOWNSCALE:
+            raise ValueError(f"max_downscale {max_downscale!r}: an integer from 16 (the default) to {MAX_DOWNSCALE}")
+        self.max_downscale, self.max_taps = max_downscale, 4 * max_downscale + 1
         if not 1 <= int(decode_threads) <= MAX_DECODE_THREADS:
             raise ValueError(f"decode_threads {decode_threads} outside 1..{MAX_DECODE_THREADS}")
         if entropy not in ("host", "device"):
@@ -553,10 +565,13 @@ class _CropStage(_UploadRing):
         # on the calling thread: at 15 us per 78 KiB file the pool's hand-over costs more than the work (1.9 ms against 6.1 ms
         # per 128 files, profiles/jpeg_microbench.txt line (g))
         batch = ops.jpeg_scan_prepare_batch(datas, [placed[s][1:] for s in enc], lambda kind, nbytes: alloc(nbytes, kind),
-                                            host.numel(), None)
+                                            host.numel(), None, self.jpeg_scans)
         if batch.out_offs != [placed[s][0] for s in enc]:
             raise ops.VtxError("vtx: the decoder's output offsets do not match the packed layout of the sources")
-        n = len(enc)
+        # jpeg_scans="any": the progressive / multi-scan files take the host stage, before anything is launched; the status and
+        # everything below that is per file of the device entropy stage covers the other files (batch.dev_ids)
+        staged = ops.jpeg_multiscan_decode(batch, datas, lambda kind, nbytes: alloc(nbytes, kind)) if batch.host_ids else None
+        n = len(batch.dev_ids)
         buf = torch.empty(batch.out_end, dtype=torch.uint8, device=dev)
         if host.numel():
             buf[:host.numel()].copy_(host, non_blocking=True)
@@ -566,13 +581,16 @@ class _CropStage(_UploadRing):
         coef, status = ops.jpeg_entropy_device(batch, dstream, cap=self._jpeg_cap)
         slots["jsegs"][1].record()
         slots["jscans"][1].record()
-        st_host, st_ev = self._pinned(n, torch.int32, "jstatus")
+        if staged is not None:
+            ops.jpeg_multiscan_upload(batch, staged, coef)
+            slots["jmscoefs"][1].record()
+        st_host, st_ev = self._pinned(max(n, 1), torch.int32, "jstatus")
         st_host[:n].copy_(status, non_blocking=True)
         st_ev.record()
         ops.jpeg_decode(coef, batch.plans, buf)
         self.jpeg_batches += 1
         slots["jplans"][1].record()
-        self._jpeg_pending = (self.jpeg_batches, st_host[:n], st_ev, list(enc))
+        self._jpeg_pending = (self.jpeg_batches, st_host[:n], st_ev, [enc[i] for i in batch.dev_ids])
         # jpeg_status="late" (the default): nothing is read here; the next call, or check_jpeg_status(), raises for a corrupt file
         # and for one that did not converge.  "wait": the status is read inside the call -- the wait is for an event recorded
         # before the launches above were queued behind it -- a file that did not converge goes through the host stage and the
@@ -580,15 +598,15 @@ class _CropStage(_UploadRing):
         # segments has at least that many subsequences, so a batch without such a file is not waited for.
         if self.jpeg_status == "wait" and batch.may_not_converge:
             st_ev.synchronize()
-            redo = [i for i, st in enumerate(st_host[:n].tolist()) if st == ops.JPEG_NOT_CONVERGED]
+            redo = [j for j, st in enumerate(st_host[:n].tolist()) if st == ops.JPEG_NOT_CONVERGED]
             if redo:
-                ops.jpeg_host_fallback(batch, datas, redo, coef)
+                ops.jpeg_host_fallback(batch, datas, [batch.dev_ids[j] for j in redo], coef)
                 st_host[:n][redo] = 0
                 ops.jpeg_decode(coef, batch.plans, buf)
                 slots["jplans"][1].record()
                 self.jpeg_fallbacks += len(redo)
             self.check_jpeg_status()
-        self.upload_bytes = host.numel() + batch.upload_bytes
+        self.upload_bytes = host.numel() + batch.upload_bytes + (staged[0].numel() if staged is not None else 0)
         return buf, placed
 
     def upload_crops(self, images, records, dev):
@@ -602,7 +620,7 @@ class _CropStage(_UploadRing):
         self.check_jpeg_status()
         for rec in records:
             h, w = images[rec["source"]].shape[:2]
-            check_crop_record(rec, h, w, rec["out_hw"])
+            check_crop_record(rec, h, w, rec["out_hw"], self.max_taps)
         slots = {}
 
         def alloc(nbytes, kind="images"):
@@ -624,7 +642,8 @@ class _CropStage(_UploadRing):
         if self.entropy == "device":
             return self._entropy_on_device(images, enc, placed, host, slots, alloc, dev)
         coef, plans, _, offs, end = ops.jpeg_entropy_batch([images[s].data for s in enc], [placed[s][1:] for s in enc],
-                                                           lambda kind, nbytes: alloc(nbytes, kind), host.numel(), self._pool)
+                                                           lambda kind, nbytes: alloc(nbytes, kind), host.numel(), self._pool,
+                                                           self.jpeg_scans)
         if offs != [placed[s][0] for s in enc]:
             raise ops.VtxError("vtx: the decoder's output offsets do not match the packed layout of the sources")
         buf = torch.empty(end, dtype=torch.uint8, device=dev)
@@ -652,7 +671,7 @@ class _CropStage(_UploadRing):
     def run_crops_by_size(self, images, plans, dev, boxes=None):
         """``run_crops`` before the split into plans: -> [(js, uint8 (len(js) * N, 3, S_h, S_w))], one entry per distinct
         output size; ``js`` = the indices of the plans of that size, whose batches follow each other in the tensor."""
-        images = _as_images(images)
+        images = _as_images(images, self.jpeg_scans)
         records = []
         for k, im in enumerate(images):
             for j, plan in enumerate(plans):
@@ -666,7 +685,14 @@ class _CropStage(_UploadRing):
             js = [j for j, p in enumerate(plans) if p.out_hw == hw]
             recs = [r for j in js for r in records if r["plan"] == j]          # plan-major: each plan's batch is contiguous
             table = self.upload(pack_crop_table(recs, placed), dev, "crops")
-            out.append((js, ops.resized_crop(buf, table, hw)))
+            if self.max_taps == MAX_TAPS:
+                out.append((js, ops.resized_crop(buf, table, hw)))
+                continue
+            # max_downscale > 16: the records with more than 65 taps on an axis are filled by a second launch
+            far = [i for i, r in enumerate(recs) if max(resample_taps(r["box"][2], r["res"][0]),
+                                                        resample_taps(r["box"][3], r["res"][1])) > MAX_TAPS]
+            idx = self.upload(torch.tensor(far, dtype=torch.int32), dev, "crops_long") if far else []
+            out.append((js, ops.resized_crop(buf, table, hw, max_taps=self.max_taps, long_records=idx)))
         return out
 
 
@@ -688,7 +714,8 @@ class DeviceMixPipeline(_CropStage):
     crops of a batch are drawn first, image by image (``boxes`` = [(top, left, h, w, flip)] overrides the draws)."""
 
     def __init__(self, mixup=0.2, cutmix=1, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), erase=None, seed=None,
-                 output="nchw_fp32", randaug=None, mix_before_aug=True, crop=None, decode_threads=8, entropy="host", jpeg_status="late"):
+                 output="nchw_fp32", randaug=None, mix_before_aug=True, crop=None, decode_threads=8, entropy="host", jpeg_status="late",
+                 max_downscale=16, jpeg_scans="single"):
         if output not in ("nchw_fp32", "nhwc_bf16"):
             raise ValueError(output)
         if randaug is not None and not mix_before_aug:
@@ -698,7 +725,7 @@ class DeviceMixPipeline(_CropStage):
         self.randaug, self.crop = randaug, crop
         self.mean, self.std = torch.tensor(mean, dtype=torch.float32), torch.tensor(std, dtype=torch.float32)
         self.rng = _random.Random(seed) if seed is not None else _random
-        super().__init__(decode_threads, entropy, jpeg_status)
+        super().__init__(decode_threads, entropy, jpeg_status, max_downscale, jpeg_scans)
 
     def pack(self, plans):
         """-> (plan table uint8 [N * vtx_mix_plan_bytes()], fill table fp32 or None)"""
@@ -757,10 +784,10 @@ class DeviceEvalPipeline(_CropStage):
     JPEGs (bytes, decoded on the device) -> the normalised batch, ``output`` as in DeviceMixPipeline."""
 
     def __init__(self, valid_size, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), output="nchw_fp32", resize=None,
-                 device="cuda", decode_threads=8, entropy="host", jpeg_status="late"):
+                 device="cuda", decode_threads=8, entropy="host", jpeg_status="late", max_downscale=16, jpeg_scans="single"):
         if output not in ("nchw_fp32", "nhwc_bf16"):
             raise ValueError(output)
-        super().__init__(decode_threads, entropy, jpeg_status)
+        super().__init__(decode_threads, entropy, jpeg_status, max_downscale, jpeg_scans)
         self.plan, self.output, self.device = CenterCropPlan(valid_size, resize), output, torch.device(device)
         self.mean, self.std = torch.tensor(mean, dtype=torch.float32), torch.tensor(std, dtype=torch.float32)
         self._tables = {}                         # the trivial normalise plan per batch size, on the device
@@ -783,8 +810,8 @@ class DeviceMultiCrop(_CropStage):
     uploaded and decoded on the device).  The draws run image by image, crop by crop.  DINOAugment's flip / ColorJitter / grayscale /
     GaussianBlur / solarize after the crop are ``DeviceDinoAugment``'s."""
 
-    def __init__(self, plans, device="cuda", decode_threads=8, entropy="host", jpeg_status="late"):
-        super().__init__(decode_threads, entropy, jpeg_status)
+    def __init__(self, plans, device="cuda", decode_threads=8, entropy="host", jpeg_status="late", max_downscale=16, jpeg_scans="single"):
+        super().__init__(decode_threads, entropy, jpeg_status, max_downscale, jpeg_scans)
         self.plans, self.device = list(plans), torch.device(device)
 
     def __call__(self, images, boxes=None):
@@ -923,10 +950,10 @@ class DeviceDinoAugment(_CropStage):
 
     def __init__(self, global_crop_size, local_crop_size, global_crop_scale, local_crop_scale, n_local_crop,
                  mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), output="nchw_fp32", generator=None, rng=None, seed=None,
-                 device="cuda", decode_threads=8, entropy="host", jpeg_status="late"):
+                 device="cuda", decode_threads=8, entropy="host", jpeg_status="late", max_downscale=16, jpeg_scans="single"):
         if output not in ("nchw_fp32", "nhwc_bf16"):
             raise ValueError(output)
-        super().__init__(decode_threads, entropy, jpeg_status)
+        super().__init__(decode_threads, entropy, jpeg_status, max_downscale, jpeg_scans)
         if rng is None and seed is not None:
             rng = _random.Random(seed)
         self.plan = DinoAugmentPlan(global_crop_size, local_crop_size, global_crop_scale, local_crop_scale, n_local_crop,
@@ -938,7 +965,7 @@ class DeviceDinoAugment(_CropStage):
 
     def augment_u8(self, images, params=None):
         """The uint8 stages: -> [(js, uint8 (len(js) * N, 3, S, S))] per crop size (run_crops_by_size's layout)."""
-        images = _as_images(images)
+        images = _as_images(images, self.jpeg_scans)
         crops = self.plan.crops
         if params is None:
             params = self.plan.draw([im.shape[:2] for im in images])

@@ -5,7 +5,10 @@ caching allocator, enqueues on torch's current HIP stream and returns tensors.  
 tensors, wrong dtypes or a missing library raise VtxError.
 """
 import ctypes
+import math
 import os
+import struct
+import threading
 
 import torch
 
@@ -1140,23 +1143,71 @@ def resample_coeffs(length, size, first=0, n=None):
     return raw[:n], raw[n:2 * n], raw[2 * n:].view(taps, n).t().contiguous()
 
 
-def resized_crop(buffer, table, out_hw):
+RESAMPLE_LONG_MAX_TAPS = 513                      # vtx_resized_crop_long: crop side / output side <= 128
+
+
+def resample_long_records(table, classic_taps=65):
+    """Host bytes of a crop table (64-byte records) -> ([indices of the records with more than ``classic_taps`` filter taps on
+    an axis], the largest tap count among them or 0).  A record with a non-positive size has no taps: the kernel zero-fills it."""
+    raw = bytes(table.cpu().numpy()) if isinstance(table, torch.Tensor) else bytes(table)
+    idx, most = [], 0
+    for k in range(len(raw) // 64):
+        f = struct.unpack_from("<q13i", raw, 64 * k)
+        ch, cw, rh, rw = f[6:10]
+        if min(ch, cw, rh, rw) < 1:
+            continue
+        taps = max(int(math.ceil(2.0 * max(ch / rh, 1.0))) * 2 + 1, int(math.ceil(2.0 * max(cw / rw, 1.0))) * 2 + 1)
+        if taps > classic_taps:
+            idx.append(k)
+            most = max(most, taps)
+    return idx, most
+
+
+def resized_crop(buffer, table, out_hw, max_taps=65, long_records=None):
     """Crop + BICUBIC resize + flip of decoded uint8 RGB sources on the device, bit-exact to PIL's
     ``img.crop(box).resize(size, BICUBIC)``: ``buffer`` = uint8 device bytes holding the sources (H x W x 3 interleaved),
     ``table`` = the uint8 device table of M records (one per output image) that vtx.input_pipeline.pack_crop_table
     builds for the buffer vtx.input_pipeline.pack_sources laid out.
-    -> uint8 (M, 3, S_h, S_w)."""
+    -> uint8 (M, 3, S_h, S_w).
+
+    ``max_taps`` = 65 (the default): one launch, crop side / output side <= 16; a record beyond that is zero-filled.  Up to 513
+    (ratio 128): the records with more than 65 taps are filled by a second launch (vtx_resized_crop_long); a table without such
+    a record launches exactly what the default launches.  ``long_records``: the indices of those records, a host list or an
+    int32 device tensor (the pipelines know them from the host records); None reads the table back from the device to find
+    them, which waits for the stream, and raises for a record with more than ``max_taps`` taps before anything is launched."""
     _dev(buffer, table)
     s_h, s_w = (out_hw, out_hw) if isinstance(out_hw, int) else out_hw
     if buffer.dtype != torch.uint8 or table.dtype != torch.uint8 or table.numel() % resample_plan_bytes():
         raise VtxError(f"vtx: resized_crop takes a uint8 source buffer and a uint8 table of {resample_plan_bytes()}-byte records")
+    if not isinstance(max_taps, int) or not resample_max_taps() <= max_taps <= RESAMPLE_LONG_MAX_TAPS:
+        raise VtxError(f"vtx: resized_crop max_taps {max_taps!r} outside {resample_max_taps()}..{RESAMPLE_LONG_MAX_TAPS}")
     m = table.numel() // resample_plan_bytes()
     lib = _lib.load()
+    idx = None
+    if max_taps > resample_max_taps():
+        if long_records is None:
+            long_records, most = resample_long_records(table, resample_max_taps())
+            if most > max_taps:
+                raise VtxError(f"vtx: a crop record needs {most} filter taps, max_taps is {max_taps}")
+        if isinstance(long_records, torch.Tensor):
+            if long_records.dtype != torch.int32 or long_records.device != buffer.device or long_records.dim() != 1:
+                raise VtxError("vtx: long_records must be a list or a one-dimensional int32 tensor on the buffer's device")
+            idx = long_records if long_records.numel() else None
+        elif len(long_records):
+            if min(long_records) < 0 or max(long_records) >= m:
+                raise VtxError(f"vtx: long_records outside the {m} records of the table")
+            idx = torch.tensor(list(long_records), dtype=torch.int32).to(buffer.device)
     out = torch.empty((m, 3, s_h, s_w), dtype=torch.uint8, device=buffer.device)
     nws = lib.vtx_resample_workspace_bytes(m, s_h, s_w)
     ws = torch.empty(max(nws // 4, 1), dtype=torch.int32, device=buffer.device)
     check(lib.vtx_resized_crop(_p(buffer), buffer.numel(), _p(table), _p(ws), nws, _p(out), m, s_h, s_w, _stream()),
           "vtx_resized_crop")
+    if idx is not None:
+        n = idx.numel()
+        nws = lib.vtx_resample_long_workspace_bytes(n, s_h, s_w, max_taps)
+        ws = torch.empty(max(nws // 4, 1), dtype=torch.int32, device=buffer.device)
+        check(lib.vtx_resized_crop_long(_p(buffer), buffer.numel(), _p(table), _p(idx), n, max_taps, _p(ws), nws, _p(out), m,
+                                        s_h, s_w, _stream()), "vtx_resized_crop_long")
     return out
 
 
@@ -1166,7 +1217,17 @@ JPEG_REASONS = {1: "not a JPEG, or a malformed header", 2: "progressive (SOF2)",
                 9: "an Adobe marker declaring a transform other than YCbCr", 10: "component ids R, G, B without JFIF (an RGB file)",
                 11: "height given by a DNL marker", 12: "zero width or height", 13: "corrupt or truncated entropy-coded data",
                 14: "window outside the image, or coefficients outside the buffer",
-                15: "more than 2^26 blocks or 2^28 pixels to store (decode a smaller window)"}
+                15: "more than 2^26 blocks or 2^28 pixels to store (decode a smaller window), or a multi-scan image of more than 2^22 blocks",
+                16: "invalid scan script", 17: "incomplete progression"}
+JPEG_KINDS = {0: "single scan", 1: "multi-scan sequential", 2: "progressive"}     # JpegInfo.reserved[0] under scans="any"
+
+
+def _jpeg_scans(scans):
+    """``scans`` = "single" (one interleaved scan: progressive and multi-scan files are refused, reasons 2 and 8) or "any"
+    (they go through the multi-scan host stage, csrc/jpeg_multiscan.h) -> the flags of vtx_jpeg_info_ex."""
+    if scans not in ("single", "any"):
+        raise ValueError(f"scans {scans!r}: 'single' or 'any'")
+    return 1 if scans == "any" else 0
 
 
 def _jpeg_ptr(data):
@@ -1186,11 +1247,15 @@ def jpeg_plan_bytes():
     return _lib.load().vtx_jpeg_plan_bytes()
 
 
-def jpeg_info(data, check=True):
+def jpeg_info(data, check=True, scans="single"):
     """Host only: the headers of an encoded JPEG -> a filled _lib.JpegInfo (width, height, ncomp, hs, vs, mcux, mcuy, reason,
-    restart).  ``check``: raise VtxError for a file the decoder refuses (``reason`` != 0) instead of returning it."""
+    restart).  ``check``: raise VtxError for a file the decoder refuses (``reason`` != 0) instead of returning it.
+    ``scans="any"``: progressive and multi-scan sequential files are accepted; ``info.reserved[0]`` is the kind (JPEG_KINDS)."""
     info = _lib.JpegInfo()
-    rc = _lib.load().vtx_jpeg_info(_jpeg_ptr(data), len(data), ctypes.byref(info))
+    if _jpeg_scans(scans):
+        rc = _lib.load().vtx_jpeg_info_ex(_jpeg_ptr(data), len(data), ctypes.byref(info), 1)
+    else:
+        rc = _lib.load().vtx_jpeg_info(_jpeg_ptr(data), len(data), ctypes.byref(info))
     if rc != 0 and (check or info.reason == 0):
         raise VtxError(f"vtx_jpeg_info: not a supported JPEG: {JPEG_REASONS.get(info.reason, 'bad arguments')} "
                        f"(code {rc}, reason {info.reason})")
@@ -1206,10 +1271,31 @@ def jpeg_plane_bytes(info, window=None):
     return _lib.load().vtx_jpeg_plane_bytes(ctypes.byref(info), _jpeg_window(window))
 
 
-def jpeg_entropy_decode(data, coef, offs, plan, window=None):
+def jpeg_scratch_bytes(info):
+    """Bytes of the whole-image scratch the multi-scan host stage needs for this file: 0 for a single-scan file, and 0 for an
+    image of more than 2^22 blocks (which it refuses)."""
+    return _lib.load().vtx_jpeg_scratch_bytes(ctypes.byref(info))
+
+
+_jpeg_tls = threading.local()
+
+
+def _jpeg_scratch(nbytes):
+    """The calling thread's pageable scratch of the multi-scan host stage, grown on demand (one per decode-pool thread)."""
+    buf = getattr(_jpeg_tls, "scratch", None)
+    if buf is None or buf.numel() < nbytes:
+        buf = _jpeg_tls.scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8)
+    return buf
+
+
+def jpeg_entropy_decode(data, coef, offs, plan, window=None, scans="single", info=None):
     """Host only, releases the GIL: the Huffman bit stream of one encoded JPEG -> its coefficient blocks at byte ``offs[0]`` of
     the host tensor ``coef`` and its plan record into the host uint8 tensor ``plan`` (jpeg_plan_bytes() bytes).  ``offs`` =
-    (coefficient, plane, output) byte offsets of the image in the three buffers of ``jpeg_decode``."""
+    (coefficient, plane, output) byte offsets of the image in the three buffers of ``jpeg_decode``.
+    ``scans="any"``: a progressive or multi-scan file is decoded scan by scan in the calling thread's scratch (``info``: its
+    ``jpeg_info(data, scans="any")`` when the caller has it)."""
+    if _jpeg_scans(scans):
+        return _jpeg_entropy_decode_ms(data, coef, offs, plan, window, info)
     if coef.is_cuda or plan.is_cuda or not coef.is_contiguous() or not plan.is_contiguous():
         raise VtxError("vtx: jpeg_entropy_decode writes contiguous HOST tensors")
     if plan.dtype != torch.uint8 or plan.numel() != jpeg_plan_bytes():
@@ -1223,15 +1309,35 @@ def jpeg_entropy_decode(data, coef, offs, plan, window=None):
                        f"(code {rc}, reason {reason.value})")
 
 
-def jpeg_entropy_batch(datas, windows=None, alloc=None, out_base=0, pool=None):
+def _jpeg_entropy_decode_ms(data, coef, offs, plan, window, info):
+    if coef.is_cuda or plan.is_cuda or not coef.is_contiguous() or not plan.is_contiguous():
+        raise VtxError("vtx: jpeg_entropy_decode writes contiguous HOST tensors")
+    if plan.dtype != torch.uint8 or plan.numel() != jpeg_plan_bytes():
+        raise VtxError(f"vtx: the plan record is {jpeg_plan_bytes()} uint8 bytes")
+    info = jpeg_info(data, scans="any") if info is None else info
+    nscratch = jpeg_scratch_bytes(info)
+    if info.reserved[0] != 0 and nscratch == 0:
+        raise VtxError(f"vtx_jpeg_entropy_decode_ms: not a supported JPEG: {JPEG_REASONS[15]} (reason 15)")
+    scratch = _jpeg_scratch(nscratch) if nscratch else None
+    reason = ctypes.c_int(0)
+    o = (ctypes.c_longlong * 3)(*[int(v) for v in offs])
+    rc = _lib.load().vtx_jpeg_entropy_decode_ms(_jpeg_ptr(data), len(data), _jpeg_window(window), coef.data_ptr(),
+                                                coef.numel() * coef.element_size(), o, plan.data_ptr(),
+                                                scratch.data_ptr() if nscratch else None, nscratch, ctypes.byref(reason))
+    if rc != 0:
+        raise VtxError(f"vtx_jpeg_entropy_decode_ms: not a supported JPEG: {JPEG_REASONS.get(reason.value, 'bad arguments')} "
+                       f"(code {rc}, reason {reason.value})")
+
+
+def jpeg_entropy_batch(datas, windows=None, alloc=None, out_base=0, pool=None, scans="single"):
     """The host stage of a batch: headers, layout, entropy decode of every file (through ``pool.map`` when a thread pool is
     given).  ``windows[i]`` = (row0, col0, rows, cols) or None; ``alloc(kind, nbytes)`` -> host uint8 tensor for kind "coefs" /
     "jplans" (pinned staging memory; default fresh tensors); the images' pixels are laid out one after the other from byte
-    ``out_base`` of the output buffer.  Raises VtxError for a refused file.
+    ``out_base`` of the output buffer.  Raises VtxError for a refused file.  ``scans``: as ``jpeg_info``.
     -> (coef uint8 host tensor, plan table uint8 host tensor, [info], [output byte offset], output end)"""
     n = len(datas)
     windows = [None] * n if windows is None else windows
-    infos = [jpeg_info(d) for d in datas]
+    infos = [jpeg_info(d, scans=scans) for d in datas]
     pb = jpeg_plan_bytes()
     offs, co, po, oo = [], 0, 0, int(out_base)
     for info, win in zip(infos, windows):
@@ -1244,7 +1350,7 @@ def jpeg_entropy_batch(datas, windows=None, alloc=None, out_base=0, pool=None):
         co, po, oo = co + cb, po + cb // 2, oo + rows * cols * 3
     alloc = alloc or (lambda kind, nbytes: torch.empty(nbytes, dtype=torch.uint8))
     coef, plans = alloc("coefs", max(co, 1))[:max(co, 1)], alloc("jplans", n * pb)[:n * pb]
-    job = lambda i: jpeg_entropy_decode(datas[i], coef, offs[i], plans[i * pb:(i + 1) * pb], windows[i])
+    job = lambda i: jpeg_entropy_decode(datas[i], coef, offs[i], plans[i * pb:(i + 1) * pb], windows[i], scans, infos[i])
     list(pool.map(job, range(n)) if pool is not None and n > 1 else map(job, range(n)))
     return coef[:co], plans, infos, [o[2] for o in offs], oo
 
@@ -1316,16 +1422,22 @@ def jpeg_round_cap():
     return _lib.load().vtx_jpeg_round_cap()
 
 
-def jpeg_scan_prepare_batch(datas, windows=None, alloc=None, out_base=0, pool=None):
+def jpeg_scan_prepare_batch(datas, windows=None, alloc=None, out_base=0, pool=None, scans="single"):
     """The host part of the device entropy stage for a batch: headers, layout, then per file (through ``pool.map`` when a thread
     pool is given) the plan record, the scan record, the segment table and the entropy-coded bytes without their stuffed zeros
     and markers.  ``alloc(kind, nbytes)`` -> host uint8 tensor for kind "jstream" / "jsegs" / "jscans" / "jplans" (pinned
     staging memory; default fresh tensors).  Raises VtxError for a refused file, a restart marker out of sequence included.
+    ``scans="any"``: the progressive and multi-scan files of the batch (``host_ids``) get their room in the coefficient buffer
+    and their plan record, but no scan record: ``jpeg_multiscan_decode`` / ``jpeg_multiscan_upload`` fill those through the
+    host stage; the scan table, the status and everything the device entropy stage sees hold the other files (``dev_ids``).
     -> JpegScanBatch"""
     lib = _lib.load()
     n = len(datas)
     windows = [None] * n if windows is None else windows
-    infos = [jpeg_info(d) for d in datas]
+    infos = [jpeg_info(d, scans=scans) for d in datas]
+    dev_ids = [i for i in range(n) if infos[i].reserved[0] == 0 or scans == "single"]
+    host_ids = [i for i in range(n) if i not in set(dev_ids)]
+    nd, row = len(dev_ids), {i: j for j, i in enumerate(dev_ids)}
     pb, sb = jpeg_plan_bytes(), jpeg_scan_bytes()
     offs, co, po, oo, so, go, no = [], 0, 0, int(out_base), 0, 0, 0
     for d, info, win in zip(datas, infos, windows):
@@ -1333,33 +1445,76 @@ def jpeg_scan_prepare_batch(datas, windows=None, alloc=None, out_base=0, pool=No
         if cb == 0:
             raise VtxError(f"vtx: JPEG decode window {win} outside the {info.height} x {info.width} image, or more than 2^26 blocks "
                            f"/ 2^28 pixels to store (nothing is allocated for such a file)")
-        nstream = lib.vtx_jpeg_scan_stream_bytes(_jpeg_ptr(d), len(d))
-        nseg = lib.vtx_jpeg_scan_segment_bytes(ctypes.byref(info))
-        nsub = lib.vtx_jpeg_scan_subsequences(ctypes.byref(info), nstream)
-        if nstream == 0 or nseg == 0 or nsub == 0:
-            raise VtxError("vtx: an entropy-coded segment of 2^28 bytes or more is not decoded on the device")
+        if info.reserved[0] != 0 and scans == "any":                    # the host stage: no stream, segments or subsequences
+            if jpeg_scratch_bytes(info) == 0:
+                raise VtxError(f"vtx: not a supported JPEG: {JPEG_REASONS[15]} (reason 15)")
+            nstream = nseg = nsub = 0
+        else:
+            nstream = lib.vtx_jpeg_scan_stream_bytes(_jpeg_ptr(d), len(d))
+            nseg = lib.vtx_jpeg_scan_segment_bytes(ctypes.byref(info))
+            nsub = lib.vtx_jpeg_scan_subsequences(ctypes.byref(info), nstream)
+            if nstream == 0 or nseg == 0 or nsub == 0:
+                raise VtxError("vtx: an entropy-coded segment of 2^28 bytes or more is not decoded on the device")
         rows, cols = (info.height, info.width) if win is None else (win[2], win[3])
         offs.append((co, po, oo, so, go, no))
         co, po, oo, so, go, no = co + cb, po + cb // 2, oo + rows * cols * 3, so + nstream, go + nseg, no + nsub
     alloc = alloc or (lambda kind, nbytes: torch.empty(nbytes, dtype=torch.uint8))
     stream, segs = alloc("jstream", so)[:so], alloc("jsegs", go)[:go]
-    scans, plans = alloc("jscans", n * sb)[:n * sb], alloc("jplans", n * pb)[:n * pb]
+    recs, plans = alloc("jscans", nd * sb)[:nd * sb], alloc("jplans", n * pb)[:n * pb]
 
     def job(i):
         reason = ctypes.c_int(0)
         o = (ctypes.c_longlong * 6)(*offs[i])
         rc = lib.vtx_jpeg_scan_prepare(_jpeg_ptr(datas[i]), len(datas[i]), _jpeg_window(windows[i]), o, stream.data_ptr(), so,
-                                       segs.data_ptr(), go, scans.data_ptr() + i * sb, plans.data_ptr() + i * pb, ctypes.byref(reason))
+                                       segs.data_ptr(), go, recs.data_ptr() + row[i] * sb, plans.data_ptr() + i * pb, ctypes.byref(reason))
         if rc != 0:
             raise VtxError(f"vtx_jpeg_scan_prepare: not a supported JPEG: {JPEG_REASONS.get(reason.value, 'bad arguments')} "
                            f"(code {rc}, reason {reason.value})")
 
-    list(pool.map(job, range(n)) if pool is not None and n > 1 else map(job, range(n)))
+    list(pool.map(job, dev_ids) if pool is not None and nd > 1 else map(job, dev_ids))
     # a segment of m subsequences is final after m rounds: only a file with a segment of jpeg_round_cap() or more can reach the cap
-    counts = scans.numpy().reshape(n, sb)[:, 40:48].copy().view("<i4")
+    counts = recs.numpy().reshape(nd, sb)[:, 40:48].copy().view("<i4")
     may_not_converge = bool(((counts[:, 1] - counts[:, 0] + 1) >= jpeg_round_cap()).any())
-    return JpegScanBatch(may_not_converge=may_not_converge, stream=stream, segs=segs, scans=scans, plans=plans, infos=infos, windows=windows, coef_bytes=co, nsub=no,
-                         coef_offs=[o[0] for o in offs], offs=offs, out_offs=[o[2] for o in offs], out_end=oo)
+    return JpegScanBatch(may_not_converge=may_not_converge, stream=stream, segs=segs, scans=recs, plans=plans, infos=infos, windows=windows, coef_bytes=co, nsub=no,
+                         coef_offs=[o[0] for o in offs], offs=offs, out_offs=[o[2] for o in offs], out_end=oo,
+                         dev_ids=dev_ids, host_ids=host_ids)
+
+
+def jpeg_multiscan_decode(batch, datas, alloc=None, pool=None):
+    """The progressive / multi-scan files of a ``jpeg_scan_prepare_batch(scans="any")`` batch through the host stage, before
+    anything is launched: their coefficients packed into one host tensor (``alloc("jmscoefs", nbytes)``: pinned staging memory;
+    default a fresh tensor) and their plan records into ``batch.plans``.  Raises VtxError for a refused file.
+    -> (host tensor, [(file index, start in it, bytes)]) for ``jpeg_multiscan_upload``"""
+    pb = jpeg_plan_bytes()
+    spans, total = [], 0
+    for i in batch.host_ids:
+        cb = jpeg_coef_bytes(batch.infos[i], batch.windows[i])
+        spans.append((i, total, cb))
+        total += cb
+    alloc = alloc or (lambda kind, nbytes: torch.empty(nbytes, dtype=torch.uint8))
+    host = alloc("jmscoefs", max(total, 1))[:max(total, 1)]
+
+    def job(span):
+        i, start, cb = span
+        # decoded at offset 0 of its own span; the record's coefficient offset is then set to the file's place in the device buffer
+        off = batch.coef_offs[i]
+        plan = batch.plans[i * pb:(i + 1) * pb]
+        jpeg_entropy_decode(datas[i], host[start:start + cb], (0, batch.offs[i][1], batch.offs[i][2]), plan, batch.windows[i], "any",
+                            batch.infos[i])
+        plan[64:72].copy_(torch.tensor([off], dtype=torch.int64).view(torch.uint8))          # VtxJpegPlan.coef_off
+
+    list(pool.map(job, spans) if pool is not None and len(spans) > 1 else map(job, spans))
+    return host[:total], spans
+
+
+def jpeg_multiscan_upload(batch, staged, coef_dev):
+    """Copies what ``jpeg_multiscan_decode`` staged to the files' offsets in the device coefficient buffer (asynchronous from
+    pinned memory: the caller keeps it unchanged until the stream has passed).  -> bytes copied"""
+    host, spans = staged
+    for i, start, cb in spans:
+        off = batch.coef_offs[i]
+        coef_dev[off:off + cb].copy_(host[start:start + cb], non_blocking=host.is_pinned())
+    return host.numel()
 
 
 def _jpeg_entropy_ws(batch):
@@ -1377,8 +1532,12 @@ def jpeg_entropy_device(batch, stream_dev=None, coef=None, ws=None, status=None,
     n, nws = _jpeg_entropy_ws(batch)
     if stream_dev is None:
         stream_dev = batch.stream.to(device, non_blocking=batch.stream.is_pinned())
-    _dev(stream_dev)
     dev = stream_dev.device
+    if n == 0:                                      # every file of the batch takes the multi-scan host stage: nothing to launch
+        coef = torch.empty(max(batch.coef_bytes, 1), dtype=torch.uint8, device=dev) if coef is None else coef
+        _dev(coef)
+        return coef, (torch.empty(0, dtype=torch.int32, device=dev) if status is None else status)
+    _dev(stream_dev)
     coef = torch.empty(max(batch.coef_bytes, 1), dtype=torch.uint8, device=dev) if coef is None else coef
     ws = torch.empty((nws + 15) // 16 * 2, dtype=torch.int64, device=dev) if ws is None else ws
     status = torch.empty(n, dtype=torch.int32, device=dev) if status is None else status
@@ -1432,25 +1591,29 @@ def jpeg_status_error(status, batch_no=None, sources=None):
     return None
 
 
-def jpeg_decode_images(datas, windows=None, device="cuda", entropy="host"):
+def jpeg_decode_images(datas, windows=None, device="cuda", entropy="host", scans="single"):
     """Encoded JPEGs -> list of uint8 (rows, cols, 3) device tensors (views of one buffer), PIL's ``convert("RGB")`` bits.
     ``entropy``: "host" (the Huffman streams on the host, the default) or "device" (csrc/jpeg_entropy.hip; this convenience
-    entry reads the status back, sends a file that did not converge through the host stage and raises for a corrupt one)."""
+    entry reads the status back, sends a file that did not converge through the host stage and raises for a corrupt one).
+    ``scans="any"``: progressive and multi-scan sequential files too; they take the host stage under either ``entropy``."""
     if entropy not in ("host", "device"):
         raise ValueError(entropy)
     if entropy == "device":
-        batch = jpeg_scan_prepare_batch(datas, windows)
+        batch = jpeg_scan_prepare_batch(datas, windows, scans=scans)
+        staged = jpeg_multiscan_decode(batch, datas) if batch.host_ids else None
         coef, status = jpeg_entropy_device(batch, device=device)
+        if staged is not None:
+            jpeg_multiscan_upload(batch, staged, coef)
         status = status.tolist()
-        redo = [i for i, s in enumerate(status) if s == JPEG_NOT_CONVERGED]
-        err = jpeg_status_error([0 if s == JPEG_NOT_CONVERGED else s for s in status])
+        redo = [batch.dev_ids[j] for j, s in enumerate(status) if s == JPEG_NOT_CONVERGED]
+        err = jpeg_status_error([0 if s == JPEG_NOT_CONVERGED else s for s in status], sources=batch.dev_ids)
         if err is not None:
             raise err
         jpeg_host_fallback(batch, datas, redo, coef)
         plans, infos, offs, end = batch.plans, batch.infos, batch.out_offs, batch.out_end
         out = jpeg_decode(coef, plans, torch.empty(end, dtype=torch.uint8, device=device))
     else:
-        coef, plans, infos, offs, end = jpeg_entropy_batch(datas, windows)
+        coef, plans, infos, offs, end = jpeg_entropy_batch(datas, windows, scans=scans)
         out = jpeg_decode(coef.to(device), plans, torch.empty(end, dtype=torch.uint8, device=device))
     res = []
     for i, (info, off) in enumerate(zip(infos, offs)):
