@@ -220,7 +220,7 @@ def test_every_truncation_and_every_single_byte_xor_returns_a_defined_reason():
     """The 37 x 53 4:2:0 progressive file cut at every length and with one byte flipped at every position: the call returns, the
     reason is a defined one, and a decode that succeeds wrote the record of that header's whole image (jpeg_plan_valid itself, a
     C function, is run on every such decode by tools/jpeg_multiscan_check.cpp)."""
-    from vtx import ops
+    from vtx import _lib, ops
     c = the_file("prog_53x37_420_q75_r0")
     d = c.jpg
     defined = set(ops.JPEG_REASONS) | {0}
@@ -239,10 +239,10 @@ def test_every_truncation_and_every_single_byte_xor_returns_a_defined_reason():
         assert reason in defined, (n, reason)
         if reason == 0:
             ok += 1
-            f = plan.numpy()[:64].view("<i4")
-            assert (f[0], f[1]) == (info.width, info.height) and f[2] == info.ncomp and (f[3], f[4]) == (info.hs, info.vs)
-            assert (f[5], f[6]) == (info.mcux, info.mcuy) and (f[7], f[8], f[9], f[10]) == (0, 0, info.mcux, info.mcuy)
-            assert (f[11], f[12], f[13], f[14]) == (0, 0, info.height, info.width)
+            f = _lib.JpegPlan.from_buffer(plan.numpy())
+            assert (f.width, f.height) == (info.width, info.height) and f.ncomp == info.ncomp and (f.hs, f.vs) == (info.hs, info.vs)
+            assert (f.mcux, f.mcuy) == (info.mcux, info.mcuy) and (f.mx0, f.my0, f.smx, f.smy) == (0, 0, info.mcux, info.mcuy)
+            assert (f.row0, f.col0, f.rows, f.cols) == (0, 0, info.height, info.width)
             assert ops.jpeg_coef_bytes(info) == coef.numel()
     assert 0 < ok < len(d)
 

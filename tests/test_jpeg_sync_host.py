@@ -44,10 +44,11 @@ def assert_equal_to_host_stage(datas, windows=None, name=None):
 
 
 def scan_fields(batch):
-    """(nseg, nsub) per image of a prepared batch (csrc/jpeg_sync.h JsScan: ints 10 and 11)."""
-    from vtx import ops
+    """(nseg, nsub) per image of a prepared batch (csrc/jpeg_sync.h JsScan)."""
+    from vtx import _lib, ops
     raw = batch.scans.numpy().reshape(-1, ops.jpeg_scan_bytes())
-    return raw[:, 40:48].copy().view("<i4")
+    heads = np.ascontiguousarray(raw[:, :ctypes.sizeof(_lib.JpegScanHead)]).view(np.dtype(_lib.JpegScanHead))[:, 0]
+    return np.stack([heads["nseg"], heads["nsub"]], axis=1)
 
 
 def edge_files():

@@ -4,70 +4,31 @@
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I vision-transformers-pytorch_amd/csrc \
 //       tools/jpeg_host_check.cpp -o jpeg_host_check && ./jpeg_host_check file.jpg [more.jpg ...]
 //
-// Per file: the whole decode, a few windows, then the file truncated at each of 20 evenly spaced lengths and with each of 50
-// seeded single-byte corruptions of its entropy-coded segment (and 50 of its headers).  Every call must return -- success or a
-// reason code -- with every write inside the buffer it was given (the buffer is allocated at exactly the advertised size, so
-// the sanitizer sees one byte too many).  Exit status 0 when nothing was flagged.
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <vector>
-
-#include "jpeg_host.h"
-
-static unsigned long long rng_state = 0x9E3779B97F4A7C15ull;
-static unsigned rnd() {
-  rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17;
-  return (unsigned)(rng_state >> 32);
-}
-
-static int runs = 0, ok = 0;
-static int reasons[16];
+// Files, windows and mutations: tools/jpeg_check_common.h.  Every call must return -- success or a reason code -- with every
+// write inside the buffer it was given (the buffer is allocated at exactly the advertised size, so the sanitizer sees one byte
+// too many).  Exit status 0 when nothing was flagged.
+#include "jpeg_check_common.h"
 
 static void decode(const std::vector<unsigned char>& d, const int* window) {
   std::vector<unsigned char> exact(d);                      // a heap copy of exactly len bytes: an over-read is flagged
-  JpegHeader hdr;
-  ++runs;
-  if (jpeg_parse_header(exact.data(), exact.size(), &hdr) != 0) { ++reasons[hdr.info.reason & 15]; return; }
-  const size_t need = jpeg_coef_bytes_of(&hdr.info, window);
-  if (need == 0) { ++reasons[VTX_JPEG_WINDOW]; return; }
+  VtxJpegInfo info;
+  ++jc_runs;
+  const int refused = jpeg_info_ex(exact.data(), exact.size(), &info, 0);
+  jc_digest(&info, sizeof(info));
+  if (refused != info.reason) { fprintf(stderr, "return code %d, reason %d\n", refused, info.reason); exit(2); }
+  if (refused) { jc_count(refused); return; }
+  const size_t need = jpeg_coef_bytes_of(&info, window);
+  if (need == 0) { jc_count(VTX_JPEG_WINDOW); return; }
   std::vector<unsigned char> coef(need);
   VtxJpegPlan plan;
   const long long offs[3] = {0, 0, 0};
   const int rc = jpeg_entropy_decode(exact.data(), exact.size(), window, coef.data(), coef.size(), offs, &plan);
-  ++reasons[rc & 15];
+  jc_count(rc);
   if (rc == 0) {
-    ++ok;
     if (!jpeg_plan_valid(plan, need, need / 2, (size_t)plan.rows * plan.cols * 3)) { fprintf(stderr, "valid decode, invalid plan\n"); exit(2); }
+    jc_digest(&plan, sizeof(plan));
+    jc_digest(coef.data(), need);
   }
 }
 
-int main(int argc, char** argv) {
-  if (argc < 2) { fprintf(stderr, "usage: %s file.jpg [...]\n", argv[0]); return 2; }
-  for (int a = 1; a < argc; ++a) {
-    FILE* f = fopen(argv[a], "rb");
-    if (!f) { perror(argv[a]); return 2; }
-    std::vector<unsigned char> d;
-    unsigned char buf[4096];
-    size_t n;
-    while ((n = fread(buf, 1, sizeof(buf), f)) > 0) d.insert(d.end(), buf, buf + n);
-    fclose(f);
-    JpegHeader hdr;
-    if (jpeg_parse_header(d.data(), d.size(), &hdr) != 0) { fprintf(stderr, "%s: refused, reason %d\n", argv[a], hdr.info.reason); return 2; }
-    const int H = hdr.info.height, W = hdr.info.width;
-    decode(d, nullptr);
-    const int wins[5][4] = {{0, 0, 1, 1}, {H - 1, W - 1, 1, 1}, {H / 2, W / 3, H - H / 2, W - W / 3}, {0, 0, H, W}, {0, 0, H + 1, W}};
-    for (const auto& w : wins) decode(d, w);
-    for (int k = 0; k < 20; ++k) decode(std::vector<unsigned char>(d.begin(), d.begin() + d.size() * k / 20), nullptr);
-    for (int k = 0; k < 100; ++k) {
-      std::vector<unsigned char> c(d);
-      const size_t lo = k < 50 ? hdr.scan_pos : 2, hi = k < 50 ? d.size() : hdr.scan_pos;
-      c[lo + rnd() % (hi - lo)] = (unsigned char)rnd();
-      decode(c, k % 3 == 0 ? wins[2] : nullptr);
-    }
-  }
-  printf("%d decodes, %d succeeded; by reason:", runs, ok);
-  for (int r = 0; r < 16; ++r) if (reasons[r]) printf(" %d:%d", r, reasons[r]);
-  printf("\n");
-  return 0;
-}
+int main(int argc, char** argv) { return jc_main(argc, argv, 0, decode); }

@@ -153,9 +153,9 @@ extern "C" {
  * accepted).  Returns 0 or VTX_ERR_JPEG. */
 int vtx_jpeg_info(const void* data, size_t len, void* info) {
   if (!data || !info) return VTX_ERR_NULL;
-  JpegHeader hdr;
-  const int rc = jpeg_parse_header((const unsigned char*)data, len, &hdr);
-  memcpy(info, &hdr.info, sizeof(VtxJpegInfo));
+  VtxJpegInfo in;
+  const int rc = jpeg_info_ex((const unsigned char*)data, len, &in, 0);
+  memcpy(info, &in, sizeof(VtxJpegInfo));
   return rc ? VTX_ERR_JPEG : VTX_OK;
 }
 

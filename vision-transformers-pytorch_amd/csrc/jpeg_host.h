@@ -1,14 +1,17 @@
 // Host entropy stage of the device JPEG decoder (csrc/jpeg.hip is the device stage): a baseline
 // JPEG's headers and Huffman bit stream -> de-zigzagged int16 coefficient blocks plus one fixed-size plan record that tells the
 // device kernels where everything is.  Plain C++17, no HIP, no mutable globals: reentrant (one call per image from any thread)
-// and compilable into a stand-alone program (tools/jpeg_host_check.cpp).
+// and compilable into a stand-alone program (tools/jpeg_host_check.cpp).  The header walk (jpeg_parse), the marker and table
+// readers and the layout helpers here also serve the multi-scan stage (csrc/jpeg_multiscan.h) and the host half of the device
+// entropy stage (csrc/jpeg_sync.h).
 //
 // Every input byte is treated as hostile: every marker length, table index, Huffman code, run length and block index is
 // checked against its bound and a failure is a reason code, never a partial image.
 //
 // Accepted: baseline sequential DCT (SOF0, or SOF1 with 8-bit tables), 8-bit samples, ONE interleaved scan, 1 component or 3
 // (YCbCr) with luma sampling (1,1), (2,1) or (2,2) and chroma 1x1, restart intervals.  Everything else is refused with its own
-// reason (VTX_JPEG_* below).
+// reason (VTX_JPEG_* below).  With the `admit` flag (bit 0 of vtx_jpeg_info_ex's flags) the walk also accepts SOF2 and scans
+// that do not hold every component; those files are decoded by csrc/jpeg_multiscan.h.
 //
 // Layout of an image's coefficients: the MCUs [mx0, mx0 + smx) x [my0, my0 + smy) the window needs (jpeg_window_mcus), as
 // component planes of blocks -- luma (smy * vs) x (smx * hs) blocks row-major, then Cb, then Cr (smy x smx each) -- 64 int16
@@ -34,8 +37,11 @@ enum {
   VTX_JPEG_ZERO_DIM = 12,       // zero width or height
   VTX_JPEG_CORRUPT = 13,        // the entropy-coded segment: bad code, run past 63, truncated data, wrong restart marker
   VTX_JPEG_WINDOW = 14,         // the caller's window is outside the image, or its coefficients outside the caller's buffer
-  VTX_JPEG_TOO_LARGE = 15       // more than JPEG_MAX_BLOCKS blocks or JPEG_MAX_PIXELS pixels to store: decode a smaller window
+  VTX_JPEG_TOO_LARGE = 15,      // more than JPEG_MAX_BLOCKS blocks or JPEG_MAX_PIXELS pixels to store: decode a smaller window
+  VTX_JPEG_SCAN_SCRIPT = 16,    // an invalid scan header or progression script, or more than JPEG_MAX_SCANS scans
+  VTX_JPEG_INCOMPLETE = 17      // EOI before coefficients 0..9 of every component were sent to the last bit (or a component at all)
 };
+enum { VTX_JPEG_KIND_SINGLE = 0, VTX_JPEG_KIND_MULTISCAN = 1, VTX_JPEG_KIND_PROGRESSIVE = 2 };   // VtxJpegInfo.reserved[0]
 
 struct VtxJpegInfo {            // 12 ints
   int width, height, ncomp;
@@ -46,7 +52,7 @@ struct VtxJpegInfo {            // 12 ints
   int reserved[3];
 };
 
-struct VtxJpegPlan {            // one per image, 480 bytes; written by jpeg_entropy_decode, checked by vtx_jpeg_decode
+struct VtxJpegPlan {            // one per image, 480 bytes; written by jpeg_fill_plan, checked by vtx_jpeg_decode
   int width, height, ncomp, hs, vs, mcux, mcuy;
   int mx0, my0, smx, smy;       // the stored MCU rectangle
   int row0, col0, rows, cols;   // the pixel window the device writes
@@ -109,13 +115,20 @@ struct JpegHuff {               // one Huffman table: 9-bit look-up plus libjpeg
   int nvals;                    // symbols the table defines
 };
 
-struct JpegHeader {
+struct JpegFrame {              // what the headers define: the frame, and the tables as currently defined
   VtxJpegInfo info;
   unsigned short qt[4][64];     // natural order
   bool qt_defined[4];
   JpegHuff dc[4], ac[4];
-  int comp_tq[3], comp_td[3], comp_ta[3];
-  size_t scan_pos;              // first byte of the entropy-coded segment
+  int comp_id[3], comp_tq[3];
+  bool progressive;             // SOF2
+  size_t scan_pos;              // first byte of the first scan's entropy-coded data
+};
+
+struct JpegScan {               // one SOS header
+  int ns, comp[3], td[3], ta[3];  // the scan's components as indices into the frame's, ascending, and their table selectors
+  int ss, se, ah, al;
+  size_t data_pos;              // first byte of the scan's entropy-coded data
 };
 
 static inline bool jpeg_build_huff(JpegHuff& h, const unsigned char* counts, const unsigned char* vals, int nvals) {
@@ -140,32 +153,123 @@ static inline bool jpeg_build_huff(JpegHuff& h, const unsigned char* counts, con
   return true;
 }
 
-// Headers up to and including SOS.  Returns VTX_JPEG_OK or the refusal; hdr->info.reason holds the same.
-static inline int jpeg_parse_header(const unsigned char* d, size_t len, JpegHeader* hdr) {
-  memset(hdr, 0, sizeof(*hdr));
-  VtxJpegInfo& in = hdr->info;
+// A DHT payload into the tables it (re)defines.  false: malformed.
+static inline bool jpeg_read_dht(const unsigned char* s, size_t n, JpegHuff* dc, JpegHuff* ac) {
+  size_t q = 0;
+  while (q < n) {
+    if (q + 17 > n) return false;
+    const int tc = s[q] >> 4, th = s[q] & 15;
+    if (tc > 1 || th > 3) return false;
+    int total = 0;
+    for (int i = 0; i < 16; ++i) total += s[q + 1 + i];
+    if (total > 256 || q + 17 + (size_t)total > n) return false;
+    if (!jpeg_build_huff(tc ? ac[th] : dc[th], s + q + 1, s + q + 17, total)) return false;
+    q += 17 + (size_t)total;
+  }
+  return true;
+}
+
+// A DQT payload.  0, or VTX_JPEG_NOT_JPEG / VTX_JPEG_PRECISION
+static inline int jpeg_read_dqt(const unsigned char* s, size_t n, unsigned short (*qt)[64], bool* defined) {
+  size_t q = 0;
+  while (q < n) {
+    const int pq = s[q] >> 4, tq = s[q] & 15;
+    if (tq > 3) return VTX_JPEG_NOT_JPEG;
+    if (pq != 0) return pq == 1 ? VTX_JPEG_PRECISION : VTX_JPEG_NOT_JPEG;
+    if (q + 65 > n) return VTX_JPEG_NOT_JPEG;
+    for (int i = 0; i < 64; ++i) qt[tq][jpeg_natural_order[i]] = s[q + 1 + i];
+    defined[tq] = true;
+    q += 65;
+  }
+  return 0;
+}
+
+// One marker at *pos (fill bytes, TEM and stray RSTn skipped): its code and payload; *pos moves behind it.  `trunc` = the reason
+// for data that ends here (VTX_JPEG_NOT_JPEG in the headers, VTX_JPEG_CORRUPT between the scans).  EOI comes back with no payload.
+static inline int jpeg_marker(const unsigned char* d, size_t len, size_t* pos, int* m, const unsigned char** s, size_t* n, int trunc) {
+  size_t p = *pos;
+  for (;;) {
+    if (p + 2 > len) return trunc;
+    if (d[p] != 0xFF) return trunc == VTX_JPEG_CORRUPT ? VTX_JPEG_CORRUPT : VTX_JPEG_NOT_JPEG;
+    while (p < len && d[p] == 0xFF) ++p;
+    if (p >= len) return trunc;
+    *m = d[p++];
+    if (*m == 0x01 || (*m >= 0xD0 && *m <= 0xD7)) continue;          // TEM, stray RSTn: no payload
+    break;
+  }
+  *s = nullptr; *n = 0;
+  if (*m == 0xD9) { *pos = p; return 0; }
+  if (*m == 0xD8 || *m == 0x00) return VTX_JPEG_NOT_JPEG;
+  if (p + 2 > len) return trunc;
+  const size_t seg = ((size_t)d[p] << 8) | d[p + 1];
+  if (seg < 2) return VTX_JPEG_NOT_JPEG;
+  if (p + seg > len) return trunc;
+  *s = d + p + 2; *n = seg - 2;
+  *pos = p + seg;
+  return 0;
+}
+
+// One SOS payload against the frame: components, tables' indices, the spectral band and the bit positions.
+static inline int jpeg_scan_header(const JpegFrame& fr, const unsigned char* s, size_t n, bool admit, JpegScan* sc) {
+  if (n < 1) return VTX_JPEG_NOT_JPEG;
+  const int ns = s[0], nc = fr.info.ncomp;
+  if (ns < 1 || ns > 4 || n != 4 + 2 * (size_t)ns) return VTX_JPEG_NOT_JPEG;
+  // a scan of fewer components than the frame: VTX_JPEG_MULTISCAN (8) without the flag, accepted with it; of more: 8 / NOT_JPEG (1)
+  if (admit ? ns > nc : ns != nc) return admit ? VTX_JPEG_NOT_JPEG : VTX_JPEG_MULTISCAN;
+  sc->ns = ns;
+  for (int i = 0; i < ns; ++i) {
+    // components in frame order, none twice: the id is looked for behind the previous one (a scan of every component thus names
+    // them position by position, also where an SOF accepted without the flag gave two components one id)
+    int c = i > 0 ? sc->comp[i - 1] + 1 : 0;
+    while (c < nc && fr.comp_id[c] != s[1 + 2 * i]) ++c;
+    if (c >= nc) return VTX_JPEG_NOT_JPEG;
+    sc->comp[i] = c;
+    sc->td[i] = s[2 + 2 * i] >> 4;
+    sc->ta[i] = s[2 + 2 * i] & 15;
+    if (sc->td[i] > 3 || sc->ta[i] > 3) return VTX_JPEG_NOT_JPEG;
+  }
+  sc->ss = s[1 + 2 * ns]; sc->se = s[2 + 2 * ns]; sc->ah = s[3 + 2 * ns] >> 4; sc->al = s[3 + 2 * ns] & 15;
+  if (fr.progressive) {
+    if (sc->ss > sc->se || sc->se > 63 || sc->al > 13) return VTX_JPEG_SCAN_SCRIPT;
+    if (sc->ss == 0 && sc->se != 0) return VTX_JPEG_SCAN_SCRIPT;     // a DC scan holds DC only
+    if (sc->ss != 0 && ns != 1) return VTX_JPEG_SCAN_SCRIPT;         // an AC scan holds one component
+    if (sc->ah != 0 && sc->al != sc->ah - 1) return VTX_JPEG_SCAN_SCRIPT;
+  } else if (sc->ss != 0 || sc->se != 63 || sc->ah != 0 || sc->al != 0) {
+    return admit ? VTX_JPEG_SCAN_SCRIPT : VTX_JPEG_NOT_JPEG;         // a sequential scan's band: NOT_JPEG (1) without the flag, SCAN_SCRIPT (16) with it
+  }
+  return 0;
+}
+
+// Whether every table a sequential scan selects is defined, its components' quantisation tables included.
+static inline bool jpeg_scan_tables_defined(const JpegFrame& fr, const JpegScan& sc) {
+  for (int i = 0; i < sc.ns; ++i)
+    if (!fr.dc[sc.td[i]].defined || !fr.ac[sc.ta[i]].defined || !fr.qt_defined[fr.comp_tq[sc.comp[i]]]) return false;
+  return true;
+}
+
+// Headers up to and including the first SOS, and that scan's header.  Returns VTX_JPEG_OK or the refusal; fr->info.reason holds
+// the same.  `admit` accepts SOF2 and scans that do not hold every component and records the kind in info.reserved[0]; every
+// place where it changes the answer is a branch on it below and in jpeg_scan_header (the table is in DESIGN.md).
+static inline int jpeg_parse(const unsigned char* d, size_t len, bool admit, JpegFrame* fr, JpegScan* first) {
+  memset(fr, 0, sizeof(*fr));
+  VtxJpegInfo& in = fr->info;
 #define JPEG_FAIL(r) do { in.reason = (r); return (r); } while (0)
   if (!d || len < 4 || d[0] != 0xFF || d[1] != 0xD8) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
   size_t p = 2;
   bool jfif = false, adobe = false, sof = false, dnl = false;
-  int adobe_transform = 0, comp_id[3] = {0, 0, 0}, comp_h[3] = {1, 1, 1}, comp_v[3] = {1, 1, 1};
+  int adobe_transform = 0, comp_h[3] = {1, 1, 1}, comp_v[3] = {1, 1, 1};
   for (;;) {
-    if (p + 2 > len) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
-    if (d[p] != 0xFF) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
-    while (p < len && d[p] == 0xFF) ++p;               // fill bytes
-    if (p >= len) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
-    const int m = d[p++];
-    if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;   // TEM, stray RSTn: no payload
-    if (m == 0xD8 || m == 0xD9 || m == 0x00) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
-    if (p + 2 > len) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
-    const size_t seg = ((size_t)d[p] << 8) | d[p + 1];
-    if (seg < 2 || p + seg > len) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
-    const unsigned char* s = d + p + 2;
-    const size_t n = seg - 2;
-    p += seg;
-    if (m == 0xC0 || m == 0xC1) {
+    int m;
+    const unsigned char* s;
+    size_t n;
+    int rc = jpeg_marker(d, len, &p, &m, &s, &n, VTX_JPEG_NOT_JPEG);
+    if (rc) JPEG_FAIL(rc);
+    if (m == 0xD9) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
+    if (m == 0xC2 && !admit) JPEG_FAIL(VTX_JPEG_PROGRESSIVE);         // SOF2: PROGRESSIVE (2) without the flag, a frame header with it
+    if (m == 0xC0 || m == 0xC1 || m == 0xC2) {
       if (sof || n < 6) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
       sof = true;
+      fr->progressive = m == 0xC2;
       if (s[0] != 8) JPEG_FAIL(VTX_JPEG_PRECISION);
       in.height = (s[1] << 8) | s[2];
       in.width = (s[3] << 8) | s[4];
@@ -173,45 +277,25 @@ static inline int jpeg_parse_header(const unsigned char* d, size_t len, JpegHead
       if (n != 6 + 3 * (size_t)in.ncomp) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
       if (in.ncomp != 1 && in.ncomp != 3) JPEG_FAIL(VTX_JPEG_COMPONENTS);
       for (int c = 0; c < in.ncomp; ++c) {
-        comp_id[c] = s[6 + 3 * c];
+        fr->comp_id[c] = s[6 + 3 * c];
         comp_h[c] = s[7 + 3 * c] >> 4;
         comp_v[c] = s[7 + 3 * c] & 15;
-        hdr->comp_tq[c] = s[8 + 3 * c];
-        if (hdr->comp_tq[c] > 3) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
+        fr->comp_tq[c] = s[8 + 3 * c];
+        if (fr->comp_tq[c] > 3) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
         if (comp_h[c] < 1 || comp_h[c] > 4 || comp_v[c] < 1 || comp_v[c] > 4) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
+        // two components of one id: not looked for without the flag (0), NOT_JPEG (1) with it
+        for (int k = 0; admit && k < c; ++k) if (fr->comp_id[k] == fr->comp_id[c]) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
       }
-    } else if (m == 0xC2) {
-      JPEG_FAIL(VTX_JPEG_PROGRESSIVE);
     } else if (m == 0xC3 || m == 0xC5 || m == 0xC6 || m == 0xC7) {
       JPEG_FAIL(VTX_JPEG_LOSSLESS);
-    } else if (m >= 0xC9 && m <= 0xCF && m != 0xCC) {
+    } else if (m >= 0xC9 && m <= 0xCF) {                  // arithmetic SOFs and DAC
       JPEG_FAIL(VTX_JPEG_ARITHMETIC);
-    } else if (m == 0xCC) {                             // DAC: arithmetic conditioning
-      JPEG_FAIL(VTX_JPEG_ARITHMETIC);
-    } else if (m == 0xC4) {                             // DHT
-      size_t q = 0;
-      while (q < n) {
-        if (q + 17 > n) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
-        const int tc = s[q] >> 4, th = s[q] & 15;
-        if (tc > 1 || th > 3) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
-        int total = 0;
-        for (int i = 0; i < 16; ++i) total += s[q + 1 + i];
-        if (total > 256 || q + 17 + (size_t)total > n) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
-        if (!jpeg_build_huff(tc ? hdr->ac[th] : hdr->dc[th], s + q + 1, s + q + 17, total)) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
-        q += 17 + (size_t)total;
-      }
-    } else if (m == 0xDB) {                             // DQT
-      size_t q = 0;
-      while (q < n) {
-        const int pq = s[q] >> 4, tq = s[q] & 15;
-        if (tq > 3) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
-        if (pq != 0) JPEG_FAIL(pq == 1 ? VTX_JPEG_PRECISION : VTX_JPEG_NOT_JPEG);
-        if (q + 65 > n) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
-        for (int i = 0; i < 64; ++i) hdr->qt[tq][jpeg_natural_order[i]] = s[q + 1 + i];
-        hdr->qt_defined[tq] = true;
-        q += 65;
-      }
-    } else if (m == 0xDD) {                             // DRI
+    } else if (m == 0xC4) {
+      if (!jpeg_read_dht(s, n, fr->dc, fr->ac)) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
+    } else if (m == 0xDB) {
+      rc = jpeg_read_dqt(s, n, fr->qt, fr->qt_defined);
+      if (rc) JPEG_FAIL(rc);
+    } else if (m == 0xDD) {
       if (n != 2) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
       in.restart = (s[0] << 8) | s[1];
     } else if (m == 0xDC) {
@@ -220,44 +304,48 @@ static inline int jpeg_parse_header(const unsigned char* d, size_t len, JpegHead
       if (n >= 5 && memcmp(s, "JFIF\0", 5) == 0) jfif = true;
     } else if (m == 0xEE) {
       if (n >= 12 && memcmp(s, "Adobe", 5) == 0) { adobe = true; adobe_transform = s[11]; }
-    } else if (m == 0xDA) {                             // SOS
+    } else if (m == 0xDA) {
       if (!sof) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
       if (dnl) JPEG_FAIL(VTX_JPEG_DNL);
       if (in.width == 0 || in.height == 0) JPEG_FAIL(VTX_JPEG_ZERO_DIM);
-      if (n < 1) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
-      const int ns = s[0];
-      if (ns < 1 || ns > 4 || n != 4 + 2 * (size_t)ns) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
-      if (ns != in.ncomp) JPEG_FAIL(VTX_JPEG_MULTISCAN);
-      for (int c = 0; c < ns; ++c) {
-        if (s[1 + 2 * c] != comp_id[c]) JPEG_FAIL(VTX_JPEG_NOT_JPEG);        // components in frame order
-        hdr->comp_td[c] = s[2 + 2 * c] >> 4;
-        hdr->comp_ta[c] = s[2 + 2 * c] & 15;
-        if (hdr->comp_td[c] > 3 || hdr->comp_ta[c] > 3) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
-        if (!hdr->dc[hdr->comp_td[c]].defined || !hdr->ac[hdr->comp_ta[c]].defined) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
-        if (!hdr->qt_defined[hdr->comp_tq[c]]) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
-      }
-      if (s[1 + 2 * ns] != 0 || s[2 + 2 * ns] != 63 || s[3 + 2 * ns] != 0) JPEG_FAIL(VTX_JPEG_NOT_JPEG);   // Ss, Se, Ah/Al
+      rc = jpeg_scan_header(*fr, s, n, admit, first);
+      if (rc) JPEG_FAIL(rc);
+      const int kind = fr->progressive ? VTX_JPEG_KIND_PROGRESSIVE : (first->ns == in.ncomp ? VTX_JPEG_KIND_SINGLE : VTX_JPEG_KIND_MULTISCAN);
+      // a table the scan selects is undefined: NOT_JPEG (1) here without the flag, ahead of the sampling checks; with it NOT_JPEG (1)
+      // behind them for a single-scan file, and at decode time (jpeg_ms_decode_image) for the other kinds
+      const bool undefined = !jpeg_scan_tables_defined(*fr, *first);
+      if (!admit && undefined) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
       if (in.ncomp == 3) {
         if (comp_h[1] != 1 || comp_v[1] != 1 || comp_h[2] != 1 || comp_v[2] != 1) JPEG_FAIL(VTX_JPEG_SAMPLING);
         if (!((comp_h[0] == 1 || comp_h[0] == 2) && (comp_v[0] == 1 || comp_v[0] == 2)) || (comp_h[0] == 1 && comp_v[0] == 2))
           JPEG_FAIL(VTX_JPEG_SAMPLING);
         if (adobe && !jfif) {
           if (adobe_transform != 1) JPEG_FAIL(VTX_JPEG_ADOBE_TRANSFORM);
-        } else if (!jfif && comp_id[0] == 'R' && comp_id[1] == 'G' && comp_id[2] == 'B') {
+        } else if (!jfif && fr->comp_id[0] == 'R' && fr->comp_id[1] == 'G' && fr->comp_id[2] == 'B') {
           JPEG_FAIL(VTX_JPEG_RGB_IDS);
         }
-        in.hs = comp_h[0]; in.vs = comp_v[0];
-      } else {
-        in.hs = in.vs = 1;
       }
+      if (admit && kind == VTX_JPEG_KIND_SINGLE && undefined) JPEG_FAIL(VTX_JPEG_NOT_JPEG);
+      in.hs = in.ncomp == 3 ? comp_h[0] : 1;
+      in.vs = in.ncomp == 3 ? comp_v[0] : 1;
       in.mcux = (in.width + 8 * in.hs - 1) / (8 * in.hs);
       in.mcuy = (in.height + 8 * in.vs - 1) / (8 * in.vs);
-      hdr->scan_pos = p;
+      in.reserved[0] = kind;
+      fr->scan_pos = first->data_pos = p;
       return VTX_JPEG_OK;
     }
     /* every other marker (APPn, COM, ...) is skipped by its length */
   }
 #undef JPEG_FAIL
+}
+
+// vtx_jpeg_info_ex: bit 0 of flags = jpeg_parse's `admit`; flags 0 is vtx_jpeg_info.
+static inline int jpeg_info_ex(const unsigned char* d, size_t len, VtxJpegInfo* info, int flags) {
+  JpegFrame fr;
+  JpegScan first;
+  const int rc = jpeg_parse(d, len, (flags & 1) != 0, &fr, &first);
+  *info = fr.info;
+  return rc;
 }
 
 // Bit reader over the entropy-coded segment: FF00 unstuffed, stops at a marker or the end of the data and pads with zero
@@ -343,67 +431,94 @@ static inline bool jpeg_decode_block(JpegBits& br, const JpegHuff& dc, const Jpe
   return !br.short_of();
 }
 
-// A header record as jpeg_parse_header fills it for an accepted file (callers of the C ABI hand these back in).
+// One restart marker, where the interval has run out: what is left of the current byte is discarded, RSTn must follow in
+// sequence (fill bytes allowed), and the reader restarts behind it.  false: corrupt.  The caller resets its predictors.
+static inline bool jpeg_restart_sync(JpegBits& br, const unsigned char* d, size_t len, int* next_rst) {
+  if (br.n - br.pad >= 8) return false;                 // a whole unread byte before the marker
+  size_t q = br.pos;
+  if (q >= len || d[q] != 0xFF) return false;
+  while (q < len && d[q] == 0xFF) ++q;
+  if (q >= len || d[q] != 0xD0 + *next_rst) return false;
+  br.pos = q + 1; br.acc = 0; br.n = 0; br.pad = 0;
+  *next_rst = (*next_rst + 1) & 7;
+  return true;
+}
+
+// The geometry an accepted header produces (jpeg_info_valid, jpeg_plan_valid: callers of the C ABI hand both records back in).
+static inline bool jpeg_geometry_valid(int width, int height, int ncomp, int hs, int vs, int mcux, int mcuy) {
+  if (width < 1 || height < 1 || width > 65535 || height > 65535) return false;
+  if (ncomp != 1 && ncomp != 3) return false;
+  if (!((hs == 1 && vs == 1) || (ncomp == 3 && hs == 2 && (vs == 1 || vs == 2)))) return false;
+  return mcux == (width + 8 * hs - 1) / (8 * hs) && mcuy == (height + 8 * vs - 1) / (8 * vs);
+}
+
 static inline bool jpeg_info_valid(const VtxJpegInfo* in) {
-  if (!in || in->reason != 0 || in->width < 1 || in->height < 1 || in->width > 65535 || in->height > 65535) return false;
-  if (in->ncomp != 1 && in->ncomp != 3) return false;
-  if (!((in->hs == 1 && in->vs == 1) || (in->ncomp == 3 && in->hs == 2 && (in->vs == 1 || in->vs == 2)))) return false;
-  return in->mcux == (in->width + 8 * in->hs - 1) / (8 * in->hs) && in->mcuy == (in->height + 8 * in->vs - 1) / (8 * in->vs);
+  return in && in->reason == 0 && jpeg_geometry_valid(in->width, in->height, in->ncomp, in->hs, in->vs, in->mcux, in->mcuy);
+}
+
+struct JpegLayout {             // what one image stores
+  int mx0, my0, smx, smy;       // the MCU rectangle of the window
+  long long nblk;               // its blocks
+};
+
+// Window -> MCU rectangle (VTX_JPEG_WINDOW), then the limits (VTX_JPEG_TOO_LARGE): JPEG_MAX_PIXELS for the window's pixels and
+// `max_blocks` for the rectangle's blocks, or for the whole image's when `whole` (the multi-scan stage, which decodes all of it).
+static inline int jpeg_layout(const VtxJpegInfo& in, const int* window, long long max_blocks, bool whole, JpegLayout* lo) {
+  if (!jpeg_window_mcus(in.width, in.height, in.ncomp, in.hs, in.vs, in.mcux, in.mcuy, window, &lo->mx0, &lo->my0, &lo->smx, &lo->smy))
+    return VTX_JPEG_WINDOW;
+  lo->nblk = jpeg_blocks(in.ncomp, in.hs, in.vs, lo->smx, lo->smy);
+  const long long limited = whole ? jpeg_blocks(in.ncomp, in.hs, in.vs, in.mcux, in.mcuy) : lo->nblk;
+  const long long npix = window ? (long long)window[2] * window[3] : (long long)in.width * in.height;
+  return limited > max_blocks || npix > JPEG_MAX_PIXELS ? VTX_JPEG_TOO_LARGE : VTX_JPEG_OK;
+}
+
+// The coefficient offset: not negative, even, and room for the blocks behind it (VTX_JPEG_WINDOW).  js_prepare, which writes no
+// coefficients, passes coef_bytes = SIZE_MAX.
+static inline int jpeg_coef_room(long long off, long long nblk, size_t coef_bytes) {
+  return off < 0 || (off & 1) || (unsigned long long)off > coef_bytes || (unsigned long long)nblk * 128 > coef_bytes - (unsigned long long)off
+             ? VTX_JPEG_WINDOW : VTX_JPEG_OK;
+}
+
+// The plan record but for its dequantisation tables.  offs = {coefficient, plane, output} byte offsets.
+static inline void jpeg_fill_plan(VtxJpegPlan* plan, const VtxJpegInfo& in, const JpegLayout& lo, const int* window, const long long* offs) {
+  plan->width = in.width; plan->height = in.height; plan->ncomp = in.ncomp; plan->hs = in.hs; plan->vs = in.vs;
+  plan->mcux = in.mcux; plan->mcuy = in.mcuy;
+  plan->mx0 = lo.mx0; plan->my0 = lo.my0; plan->smx = lo.smx; plan->smy = lo.smy;
+  plan->row0 = window ? window[0] : 0; plan->col0 = window ? window[1] : 0;
+  plan->rows = window ? window[2] : in.height; plan->cols = window ? window[3] : in.width;
+  plan->coef_off = offs[0]; plan->ws_off = offs[1]; plan->out_off = offs[2];
 }
 
 // 0 for a refused or inconsistent header, a window outside the image, or more than JPEG_MAX_BLOCKS / JPEG_MAX_PIXELS to store
 static inline size_t jpeg_coef_bytes_of(const VtxJpegInfo* in, const int* window) {
-  int mx0, my0, smx, smy;
-  if (!jpeg_info_valid(in) || !jpeg_window_mcus(in->width, in->height, in->ncomp, in->hs, in->vs, in->mcux, in->mcuy, window,
-                                                &mx0, &my0, &smx, &smy))
-    return 0;
-  const long long nblk = jpeg_blocks(in->ncomp, in->hs, in->vs, smx, smy);
-  const long long npix = window ? (long long)window[2] * window[3] : (long long)in->width * in->height;
-  if (nblk > JPEG_MAX_BLOCKS || npix > JPEG_MAX_PIXELS) return 0;
-  return (size_t)nblk * 128;
+  JpegLayout lo;
+  return jpeg_info_valid(in) && jpeg_layout(*in, window, JPEG_MAX_BLOCKS, false, &lo) == 0 ? (size_t)lo.nblk * 128 : 0;
 }
 
-// The whole host stage for one image.  coef / coef_bytes: the caller's coefficient buffer (the pinned staging memory) and its
-// size; offs = {coefficient, plane, output} byte offsets that go into the record.  Returns VTX_JPEG_OK or the reason; on
-// failure the record is zeroed (a zero record is refused by the device entry).
-static inline int jpeg_entropy_decode(const unsigned char* d, size_t len, const int* window, void* coef, size_t coef_bytes,
-                                      const long long* offs, VtxJpegPlan* plan) {
-  memset(plan, 0, sizeof(*plan));
-  JpegHeader hdr;
-  int rc = jpeg_parse_header(d, len, &hdr);
+// The entropy-coded data of a single-scan file whose headers are in fr / sc (the body of jpeg_entropy_decode).
+static inline int jpeg_decode_single(const unsigned char* d, size_t len, const JpegFrame& fr, const JpegScan& sc, const int* window,
+                                     void* coef, size_t coef_bytes, const long long* offs, VtxJpegPlan* plan) {
+  const VtxJpegInfo& in = fr.info;
+  JpegLayout lo;
+  int rc = jpeg_layout(in, window, JPEG_MAX_BLOCKS, false, &lo);
+  if (!rc) rc = jpeg_coef_room(offs[0], lo.nblk, coef_bytes);
   if (rc) return rc;
-  const VtxJpegInfo& in = hdr.info;
-  int mx0, my0, smx, smy;
-  if (!jpeg_window_mcus(in.width, in.height, in.ncomp, in.hs, in.vs, in.mcux, in.mcuy, window, &mx0, &my0, &smx, &smy))
-    return VTX_JPEG_WINDOW;
-  const long long nblk = jpeg_blocks(in.ncomp, in.hs, in.vs, smx, smy);
-  if (nblk > JPEG_MAX_BLOCKS || (window ? (long long)window[2] * window[3] : (long long)in.width * in.height) > JPEG_MAX_PIXELS)
-    return VTX_JPEG_TOO_LARGE;
-  if (offs[0] < 0 || (offs[0] & 1) || (unsigned long long)offs[0] > coef_bytes ||
-      (unsigned long long)nblk * 128 > coef_bytes - (unsigned long long)offs[0])
-    return VTX_JPEG_WINDOW;
+  const int mx0 = lo.mx0, my0 = lo.my0, smx = lo.smx, smy = lo.smy;
   int16_t* base = (int16_t*)((unsigned char*)coef + offs[0]);
   const int hs = in.hs, vs = in.vs;
   const long long luma_blocks = (long long)smx * hs * smy * vs, chroma_blocks = (long long)smx * smy;
 
-  JpegBits br = {d, hdr.scan_pos, len, 0, 0, 0};
+  JpegBits br = {d, fr.scan_pos, len, 0, 0, 0};
   uint32_t pred[3] = {0, 0, 0};
   const JpegHuff* dct[3];
   const JpegHuff* act[3];
-  for (int c = 0; c < in.ncomp; ++c) { dct[c] = &hdr.dc[hdr.comp_td[c]]; act[c] = &hdr.ac[hdr.comp_ta[c]]; }
+  for (int c = 0; c < in.ncomp; ++c) { dct[c] = &fr.dc[sc.td[c]]; act[c] = &fr.ac[sc.ta[c]]; }
   int until_restart = in.restart, next_rst = 0;
   for (int my = 0; my < in.mcuy; ++my) {
     const bool row_in = my >= my0 && my < my0 + smy;
     for (int mx = 0; mx < in.mcux; ++mx) {
       if (in.restart && until_restart == 0) {
-        // byte-align: what is left of the current byte is discarded; a whole unread byte before the marker is an error
-        if (br.n - br.pad >= 8) return VTX_JPEG_CORRUPT;
-        size_t q = br.pos;
-        if (q >= len || d[q] != 0xFF) return VTX_JPEG_CORRUPT;
-        while (q < len && d[q] == 0xFF) ++q;
-        if (q >= len || d[q] != 0xD0 + next_rst) return VTX_JPEG_CORRUPT;
-        br.pos = q + 1; br.acc = 0; br.n = 0; br.pad = 0;
-        next_rst = (next_rst + 1) & 7;
+        if (!jpeg_restart_sync(br, d, len, &next_rst)) return VTX_JPEG_CORRUPT;
         until_restart = in.restart;
         pred[0] = pred[1] = pred[2] = 0;
       }
@@ -422,23 +537,27 @@ static inline int jpeg_entropy_decode(const unsigned char* d, size_t len, const 
       if (in.restart) --until_restart;
     }
   }
-  plan->width = in.width; plan->height = in.height; plan->ncomp = in.ncomp; plan->hs = hs; plan->vs = vs;
-  plan->mcux = in.mcux; plan->mcuy = in.mcuy;
-  plan->mx0 = mx0; plan->my0 = my0; plan->smx = smx; plan->smy = smy;
-  plan->row0 = window ? window[0] : 0; plan->col0 = window ? window[1] : 0;
-  plan->rows = window ? window[2] : in.height; plan->cols = window ? window[3] : in.width;
-  plan->coef_off = offs[0]; plan->ws_off = offs[1]; plan->out_off = offs[2];
-  for (int c = 0; c < in.ncomp; ++c) memcpy(plan->q[c], hdr.qt[hdr.comp_tq[c]], 128);
+  jpeg_fill_plan(plan, in, lo, window, offs);
+  for (int c = 0; c < in.ncomp; ++c) memcpy(plan->q[c], fr.qt[fr.comp_tq[c]], 128);
   return VTX_JPEG_OK;
+}
+
+// The whole host stage for one image.  coef / coef_bytes: the caller's coefficient buffer (the pinned staging memory) and its
+// size; offs = {coefficient, plane, output} byte offsets that go into the record.  Returns VTX_JPEG_OK or the reason; on
+// failure the record is zeroed (a zero record is refused by the device entry).
+static inline int jpeg_entropy_decode(const unsigned char* d, size_t len, const int* window, void* coef, size_t coef_bytes,
+                                      const long long* offs, VtxJpegPlan* plan) {
+  memset(plan, 0, sizeof(*plan));
+  JpegFrame fr;
+  JpegScan sc;
+  const int rc = jpeg_parse(d, len, false, &fr, &sc);
+  return rc ? rc : jpeg_decode_single(d, len, fr, sc, window, coef, coef_bytes, offs, plan);
 }
 
 // What vtx_jpeg_decode checks of a record before anything is launched: consistent geometry, the stored rectangle is the one
 // the window needs, and the three ranges lie inside the buffers.  plane_bytes: the workspace's plane area.
 static inline bool jpeg_plan_valid(const VtxJpegPlan& r, size_t coef_bytes, size_t plane_bytes, size_t out_bytes) {
-  if (r.width < 1 || r.height < 1 || r.width > 65535 || r.height > 65535) return false;
-  if (r.ncomp != 1 && r.ncomp != 3) return false;
-  if (!((r.hs == 1 && r.vs == 1) || (r.ncomp == 3 && r.hs == 2 && (r.vs == 1 || r.vs == 2)))) return false;
-  if (r.mcux != (r.width + 8 * r.hs - 1) / (8 * r.hs) || r.mcuy != (r.height + 8 * r.vs - 1) / (8 * r.vs)) return false;
+  if (!jpeg_geometry_valid(r.width, r.height, r.ncomp, r.hs, r.vs, r.mcux, r.mcuy)) return false;
   const int window[4] = {r.row0, r.col0, r.rows, r.cols};
   int mx0, my0, smx, smy;
   if (!jpeg_window_mcus(r.width, r.height, r.ncomp, r.hs, r.vs, r.mcux, r.mcuy, window, &mx0, &my0, &smx, &smy)) return false;

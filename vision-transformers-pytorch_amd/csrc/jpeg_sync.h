@@ -329,20 +329,18 @@ static inline int js_prepare(const unsigned char* d, size_t len, const int* wind
                              size_t stream_cap, unsigned char* segbuf, size_t seg_cap, JsScan* sc, VtxJpegPlan* plan) {
   memset(plan, 0, sizeof(*plan));
   memset(sc, 0, sizeof(*sc));
-  JpegHeader hdr;
-  int rc = jpeg_parse_header(d, len, &hdr);
+  JpegFrame hdr;
+  JpegScan first;
+  int rc = jpeg_parse(d, len, false, &hdr, &first);
   if (rc) return rc;
   const VtxJpegInfo& in = hdr.info;
-  int mx0, my0, smx, smy;
-  if (!jpeg_window_mcus(in.width, in.height, in.ncomp, in.hs, in.vs, in.mcux, in.mcuy, window, &mx0, &my0, &smx, &smy))
-    return VTX_JPEG_WINDOW;
-  const long long nblk = jpeg_blocks(in.ncomp, in.hs, in.vs, smx, smy);
-  if (nblk > JPEG_MAX_BLOCKS || (window ? (long long)window[2] * window[3] : (long long)in.width * in.height) > JPEG_MAX_PIXELS)
-    return VTX_JPEG_TOO_LARGE;
+  JpegLayout lo;
+  rc = jpeg_layout(in, window, JPEG_MAX_BLOCKS, false, &lo);
+  if (rc) return rc;
   const size_t raw = len - hdr.scan_pos;
   if (raw >= JS_MAX_STREAM_BYTES) return VTX_JPEG_TOO_LARGE;
   const long long nseg = js_segments(in);
-  if (offs[0] < 0 || (offs[0] & 1) || offs[5] < 0) return VTX_JPEG_WINDOW;
+  if (jpeg_coef_room(offs[0], lo.nblk, SIZE_MAX) || offs[5] < 0) return VTX_JPEG_WINDOW;   // no coefficients are written here
   if (offs[3] < 0 || (unsigned long long)offs[3] > stream_cap || raw > stream_cap - (unsigned long long)offs[3]) return VTX_JPEG_WINDOW;
   if (offs[4] < 0 || (offs[4] & 3) || (unsigned long long)offs[4] > seg_cap ||
       (unsigned long long)nseg * sizeof(JsSeg) > seg_cap - (unsigned long long)offs[4])
@@ -383,25 +381,21 @@ static inline int js_prepare(const unsigned char* d, size_t len, const int* wind
     }
   }
   sc->ncomp = in.ncomp; sc->hs = in.hs; sc->vs = in.vs; sc->mcux = in.mcux; sc->mcuy = in.mcuy;
-  sc->mx0 = mx0; sc->my0 = my0; sc->smx = smx; sc->smy = smy;
+  sc->mx0 = lo.mx0; sc->my0 = lo.my0; sc->smx = lo.smx; sc->smy = lo.smy;
   sc->restart = in.restart > 0 ? in.restart : 0;
   sc->nseg = (int32_t)nseg; sc->nsub = (int32_t)nsub;
   sc->coef_off = offs[0]; sc->stream_off = offs[3]; sc->stream_bytes = (int64_t)(w - w0); sc->seg_off = offs[4]; sc->sub_off = offs[5];
-  for (int c = 0; c < in.ncomp; ++c) { js_copy_huff(sc->dc[c], hdr.dc[hdr.comp_td[c]]); js_copy_huff(sc->ac[c], hdr.ac[hdr.comp_ta[c]]); }
-  plan->width = in.width; plan->height = in.height; plan->ncomp = in.ncomp; plan->hs = in.hs; plan->vs = in.vs;
-  plan->mcux = in.mcux; plan->mcuy = in.mcuy;
-  plan->mx0 = mx0; plan->my0 = my0; plan->smx = smx; plan->smy = smy;
-  plan->row0 = window ? window[0] : 0; plan->col0 = window ? window[1] : 0;
-  plan->rows = window ? window[2] : in.height; plan->cols = window ? window[3] : in.width;
-  plan->coef_off = offs[0]; plan->ws_off = offs[1]; plan->out_off = offs[2];
+  for (int c = 0; c < in.ncomp; ++c) { js_copy_huff(sc->dc[c], hdr.dc[first.td[c]]); js_copy_huff(sc->ac[c], hdr.ac[first.ta[c]]); }
+  jpeg_fill_plan(plan, in, lo, window, offs);
   for (int c = 0; c < in.ncomp; ++c) memcpy(plan->q[c], hdr.qt[hdr.comp_tq[c]], 128);
   return VTX_JPEG_OK;
 }
 
 // Upper bounds of what js_prepare writes for a file, from its header alone; 0 for a refused file.
 static inline size_t js_stream_bytes_of(const unsigned char* d, size_t len) {
-  JpegHeader hdr;
-  if (!d || jpeg_parse_header(d, len, &hdr) != 0 || len - hdr.scan_pos >= JS_MAX_STREAM_BYTES) return 0;
+  JpegFrame hdr;
+  JpegScan first;
+  if (!d || jpeg_parse(d, len, false, &hdr, &first) != 0 || len - hdr.scan_pos >= JS_MAX_STREAM_BYTES) return 0;
   return js_align(len - hdr.scan_pos + 1, 16);
 }
 static inline size_t js_segment_bytes_of(const VtxJpegInfo* in) {

@@ -78,6 +78,19 @@ class JpegInfo(ctypes.Structure):
     _fields_ = [(n, _I) for n in ("width", "height", "ncomp", "hs", "vs", "mcux", "mcuy", "reason", "restart")] + [("reserved", _I * 3)]
 
 
+class JpegPlan(ctypes.Structure):
+    """csrc/jpeg_host.h VtxJpegPlan (load() checks sizeof against vtx_jpeg_plan_bytes())."""
+    _fields_ = ([(n, _I) for n in ("width", "height", "ncomp", "hs", "vs", "mcux", "mcuy", "mx0", "my0", "smx", "smy", "row0", "col0",
+                                   "rows", "cols", "pad")] +
+                [(n, _L) for n in ("coef_off", "ws_off", "out_off", "reserved")] + [("q", ctypes.c_uint16 * 64 * 3)])
+
+
+class JpegScanHead(ctypes.Structure):
+    """csrc/jpeg_sync.h JsScan up to ``reserved``: the fixed-size head of a scan record (the Huffman tables follow)."""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("ncomp", "hs", "vs", "mcux", "mcuy", "mx0", "my0", "smx", "smy", "restart", "nseg", "nsub")] +
+                [(n, _L) for n in ("coef_off", "stream_off", "stream_bytes", "seg_off", "sub_off", "reserved")])
+
+
 class TimerRec(ctypes.Structure):
     """include/vtx.h VtxTimerRec."""
     _fields_ = [("tag", _I), ("n", _I), ("k", _I), ("flags", _I), ("rows", _L), ("ms", _F)]
@@ -294,6 +307,8 @@ def load():
         raise VtxError("libvtx.so layer descriptors do not match the bindings (VtxLayerFwd / VtxLayerBwd): rebuild")
     if lib.vtx_layer_desc_bytes(2) != ctypes.sizeof(SrLayerFwd) or lib.vtx_layer_desc_bytes(3) != ctypes.sizeof(SrLayerBwd):
         raise VtxError("libvtx.so layer descriptors do not match the bindings (VtxSrLayerFwd / VtxSrLayerBwd): rebuild")
+    if lib.vtx_jpeg_plan_bytes() != ctypes.sizeof(JpegPlan) or lib.vtx_jpeg_scan_bytes() < ctypes.sizeof(JpegScanHead):
+        raise VtxError("libvtx.so JPEG records do not match the bindings (VtxJpegPlan / JsScan): rebuild")
     _lib = lib
     return lib
 

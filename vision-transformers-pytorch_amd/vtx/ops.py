@@ -10,6 +10,7 @@ import os
 import struct
 import threading
 
+import numpy as np
 import torch
 
 from . import _lib, options
@@ -1243,6 +1244,10 @@ def _jpeg_window(window):
     return None if window is None else (ctypes.c_int * 4)(*[int(v) for v in window])
 
 
+def _jpeg_refused(entry, rc, reason):
+    return VtxError(f"{entry}: not a supported JPEG: {JPEG_REASONS.get(reason, 'bad arguments')} (code {rc}, reason {reason})")
+
+
 def jpeg_plan_bytes():
     return _lib.load().vtx_jpeg_plan_bytes()
 
@@ -1257,8 +1262,7 @@ def jpeg_info(data, check=True, scans="single"):
     else:
         rc = _lib.load().vtx_jpeg_info(_jpeg_ptr(data), len(data), ctypes.byref(info))
     if rc != 0 and (check or info.reason == 0):
-        raise VtxError(f"vtx_jpeg_info: not a supported JPEG: {JPEG_REASONS.get(info.reason, 'bad arguments')} "
-                       f"(code {rc}, reason {info.reason})")
+        raise _jpeg_refused("vtx_jpeg_info", rc, info.reason)
     return info
 
 
@@ -1288,45 +1292,56 @@ def _jpeg_scratch(nbytes):
     return buf
 
 
+def _jpeg_host_stage(entry, data, coef, offs, plan, window, *more):
+    """One call of vtx_jpeg_entropy_decode / vtx_jpeg_entropy_decode_ms (``more``: what the latter takes behind the record)."""
+    reason = ctypes.c_int(0)
+    o = (ctypes.c_longlong * 3)(*[int(v) for v in offs])
+    rc = getattr(_lib.load(), entry)(_jpeg_ptr(data), len(data), _jpeg_window(window), coef.data_ptr(),
+                                     coef.numel() * coef.element_size(), o, plan.data_ptr(), *more, ctypes.byref(reason))
+    if rc != 0:
+        raise _jpeg_refused(entry, rc, reason.value)
+
+
 def jpeg_entropy_decode(data, coef, offs, plan, window=None, scans="single", info=None):
     """Host only, releases the GIL: the Huffman bit stream of one encoded JPEG -> its coefficient blocks at byte ``offs[0]`` of
     the host tensor ``coef`` and its plan record into the host uint8 tensor ``plan`` (jpeg_plan_bytes() bytes).  ``offs`` =
     (coefficient, plane, output) byte offsets of the image in the three buffers of ``jpeg_decode``.
     ``scans="any"``: a progressive or multi-scan file is decoded scan by scan in the calling thread's scratch (``info``: its
     ``jpeg_info(data, scans="any")`` when the caller has it)."""
-    if _jpeg_scans(scans):
-        return _jpeg_entropy_decode_ms(data, coef, offs, plan, window, info)
+    any_kind = _jpeg_scans(scans)
     if coef.is_cuda or plan.is_cuda or not coef.is_contiguous() or not plan.is_contiguous():
         raise VtxError("vtx: jpeg_entropy_decode writes contiguous HOST tensors")
     if plan.dtype != torch.uint8 or plan.numel() != jpeg_plan_bytes():
         raise VtxError(f"vtx: the plan record is {jpeg_plan_bytes()} uint8 bytes")
-    reason = ctypes.c_int(0)
-    o = (ctypes.c_longlong * 3)(*[int(v) for v in offs])
-    rc = _lib.load().vtx_jpeg_entropy_decode(_jpeg_ptr(data), len(data), _jpeg_window(window), coef.data_ptr(),
-                                             coef.numel() * coef.element_size(), o, plan.data_ptr(), ctypes.byref(reason))
-    if rc != 0:
-        raise VtxError(f"vtx_jpeg_entropy_decode: not a supported JPEG: {JPEG_REASONS.get(reason.value, 'bad arguments')} "
-                       f"(code {rc}, reason {reason.value})")
+    if any_kind:
+        return _jpeg_entropy_decode_ms(data, coef, offs, plan, window, info)
+    _jpeg_host_stage("vtx_jpeg_entropy_decode", data, coef, offs, plan, window)
 
 
 def _jpeg_entropy_decode_ms(data, coef, offs, plan, window, info):
-    if coef.is_cuda or plan.is_cuda or not coef.is_contiguous() or not plan.is_contiguous():
-        raise VtxError("vtx: jpeg_entropy_decode writes contiguous HOST tensors")
-    if plan.dtype != torch.uint8 or plan.numel() != jpeg_plan_bytes():
-        raise VtxError(f"vtx: the plan record is {jpeg_plan_bytes()} uint8 bytes")
     info = jpeg_info(data, scans="any") if info is None else info
     nscratch = jpeg_scratch_bytes(info)
     if info.reserved[0] != 0 and nscratch == 0:
         raise VtxError(f"vtx_jpeg_entropy_decode_ms: not a supported JPEG: {JPEG_REASONS[15]} (reason 15)")
-    scratch = _jpeg_scratch(nscratch) if nscratch else None
-    reason = ctypes.c_int(0)
-    o = (ctypes.c_longlong * 3)(*[int(v) for v in offs])
-    rc = _lib.load().vtx_jpeg_entropy_decode_ms(_jpeg_ptr(data), len(data), _jpeg_window(window), coef.data_ptr(),
-                                                coef.numel() * coef.element_size(), o, plan.data_ptr(),
-                                                scratch.data_ptr() if nscratch else None, nscratch, ctypes.byref(reason))
-    if rc != 0:
-        raise VtxError(f"vtx_jpeg_entropy_decode_ms: not a supported JPEG: {JPEG_REASONS.get(reason.value, 'bad arguments')} "
-                       f"(code {rc}, reason {reason.value})")
+    scratch = _jpeg_scratch(nscratch).data_ptr() if nscratch else None
+    _jpeg_host_stage("vtx_jpeg_entropy_decode_ms", data, coef, offs, plan, window, scratch, nscratch)
+
+
+def _jpeg_batch_layout(infos, windows, out_base, extra=None):
+    """Where each image of a batch goes: its (coefficient, plane, output) byte offsets, the images one after the other, the
+    pixels from byte ``out_base``; ``extra(i)`` -> three further sizes of image i that are laid out the same way.  Raises VtxError
+    for a window that stores nothing.  -> ([offsets per image], the ends)"""
+    offs, end = [], (0, 0, int(out_base)) + ((0, 0, 0) if extra else ())
+    for i, (info, win) in enumerate(zip(infos, windows)):
+        cb = jpeg_coef_bytes(info, win)
+        if cb == 0:
+            raise VtxError(f"vtx: JPEG decode window {win} outside the {info.height} x {info.width} image, or more than 2^26 blocks "
+                           f"/ 2^28 pixels to store (nothing is allocated for such a file)")
+        rows, cols = (info.height, info.width) if win is None else (win[2], win[3])
+        sizes = (cb, cb // 2, rows * cols * 3) + (extra(i) if extra else ())
+        offs.append(end)
+        end = tuple(a + b for a, b in zip(end, sizes))
+    return offs, end
 
 
 def jpeg_entropy_batch(datas, windows=None, alloc=None, out_base=0, pool=None, scans="single"):
@@ -1339,15 +1354,7 @@ def jpeg_entropy_batch(datas, windows=None, alloc=None, out_base=0, pool=None, s
     windows = [None] * n if windows is None else windows
     infos = [jpeg_info(d, scans=scans) for d in datas]
     pb = jpeg_plan_bytes()
-    offs, co, po, oo = [], 0, 0, int(out_base)
-    for info, win in zip(infos, windows):
-        cb = jpeg_coef_bytes(info, win)
-        if cb == 0:
-            raise VtxError(f"vtx: JPEG decode window {win} outside the {info.height} x {info.width} image, or more than 2^26 blocks "
-                           f"/ 2^28 pixels to store (nothing is allocated for such a file)")
-        rows, cols = (info.height, info.width) if win is None else (win[2], win[3])
-        offs.append((co, po, oo))
-        co, po, oo = co + cb, po + cb // 2, oo + rows * cols * 3
+    offs, (co, _, oo) = _jpeg_batch_layout(infos, windows, out_base)
     alloc = alloc or (lambda kind, nbytes: torch.empty(nbytes, dtype=torch.uint8))
     coef, plans = alloc("coefs", max(co, 1))[:max(co, 1)], alloc("jplans", n * pb)[:n * pb]
     job = lambda i: jpeg_entropy_decode(datas[i], coef, offs[i], plans[i * pb:(i + 1) * pb], windows[i], scans, infos[i])
@@ -1358,14 +1365,10 @@ def jpeg_entropy_batch(datas, windows=None, alloc=None, out_base=0, pool=None, s
 def _jpeg_plan_fields(plans):
     """host plan table -> (blocks, pixels, coef_off, ws_off, out_off) int64 numpy arrays, for sizing only (the library
     checks every record itself)."""
-    pb = jpeg_plan_bytes()
-    raw = plans.numpy().reshape(-1, pb)
-    i32 = raw[:, :64].copy().view("<i4")
-    i64 = raw[:, 64:96].copy().view("<i8")
-    per = i32[:, 3].astype("int64") * i32[:, 4] + 2
-    per[i32[:, 2] != 3] = 1
-    blocks = i32[:, 9].astype("int64") * i32[:, 10] * per
-    return blocks, i32[:, 13].astype("int64") * i32[:, 14], i64[:, 0], i64[:, 1], i64[:, 2]
+    r = plans.numpy().view(np.dtype(_lib.JpegPlan))
+    per = np.where(r["ncomp"] == 3, r["hs"].astype("int64") * r["vs"] + 2, 1)
+    blocks = r["smx"].astype("int64") * r["smy"] * per
+    return blocks, r["rows"].astype("int64") * r["cols"], r["coef_off"], r["ws_off"], r["out_off"]
 
 
 def jpeg_decode(coef, plans, out=None):
@@ -1439,25 +1442,21 @@ def jpeg_scan_prepare_batch(datas, windows=None, alloc=None, out_base=0, pool=No
     host_ids = [i for i in range(n) if i not in set(dev_ids)]
     nd, row = len(dev_ids), {i: j for j, i in enumerate(dev_ids)}
     pb, sb = jpeg_plan_bytes(), jpeg_scan_bytes()
-    offs, co, po, oo, so, go, no = [], 0, 0, int(out_base), 0, 0, 0
-    for d, info, win in zip(datas, infos, windows):
-        cb = jpeg_coef_bytes(info, win)
-        if cb == 0:
-            raise VtxError(f"vtx: JPEG decode window {win} outside the {info.height} x {info.width} image, or more than 2^26 blocks "
-                           f"/ 2^28 pixels to store (nothing is allocated for such a file)")
+
+    def stream_sizes(i):                                                # (stream bytes, segment table bytes, subsequences)
+        d, info = datas[i], infos[i]
         if info.reserved[0] != 0 and scans == "any":                    # the host stage: no stream, segments or subsequences
             if jpeg_scratch_bytes(info) == 0:
                 raise VtxError(f"vtx: not a supported JPEG: {JPEG_REASONS[15]} (reason 15)")
-            nstream = nseg = nsub = 0
-        else:
-            nstream = lib.vtx_jpeg_scan_stream_bytes(_jpeg_ptr(d), len(d))
-            nseg = lib.vtx_jpeg_scan_segment_bytes(ctypes.byref(info))
-            nsub = lib.vtx_jpeg_scan_subsequences(ctypes.byref(info), nstream)
-            if nstream == 0 or nseg == 0 or nsub == 0:
-                raise VtxError("vtx: an entropy-coded segment of 2^28 bytes or more is not decoded on the device")
-        rows, cols = (info.height, info.width) if win is None else (win[2], win[3])
-        offs.append((co, po, oo, so, go, no))
-        co, po, oo, so, go, no = co + cb, po + cb // 2, oo + rows * cols * 3, so + nstream, go + nseg, no + nsub
+            return 0, 0, 0
+        nstream = lib.vtx_jpeg_scan_stream_bytes(_jpeg_ptr(d), len(d))
+        nseg = lib.vtx_jpeg_scan_segment_bytes(ctypes.byref(info))
+        nsub = lib.vtx_jpeg_scan_subsequences(ctypes.byref(info), nstream)
+        if nstream == 0 or nseg == 0 or nsub == 0:
+            raise VtxError("vtx: an entropy-coded segment of 2^28 bytes or more is not decoded on the device")
+        return nstream, nseg, nsub
+
+    offs, (co, _, oo, so, go, no) = _jpeg_batch_layout(infos, windows, out_base, stream_sizes)
     alloc = alloc or (lambda kind, nbytes: torch.empty(nbytes, dtype=torch.uint8))
     stream, segs = alloc("jstream", so)[:so], alloc("jsegs", go)[:go]
     recs, plans = alloc("jscans", nd * sb)[:nd * sb], alloc("jplans", n * pb)[:n * pb]
@@ -1468,13 +1467,12 @@ def jpeg_scan_prepare_batch(datas, windows=None, alloc=None, out_base=0, pool=No
         rc = lib.vtx_jpeg_scan_prepare(_jpeg_ptr(datas[i]), len(datas[i]), _jpeg_window(windows[i]), o, stream.data_ptr(), so,
                                        segs.data_ptr(), go, recs.data_ptr() + row[i] * sb, plans.data_ptr() + i * pb, ctypes.byref(reason))
         if rc != 0:
-            raise VtxError(f"vtx_jpeg_scan_prepare: not a supported JPEG: {JPEG_REASONS.get(reason.value, 'bad arguments')} "
-                           f"(code {rc}, reason {reason.value})")
+            raise _jpeg_refused("vtx_jpeg_scan_prepare", rc, reason.value)
 
     list(pool.map(job, dev_ids) if pool is not None and nd > 1 else map(job, dev_ids))
     # a segment of m subsequences is final after m rounds: only a file with a segment of jpeg_round_cap() or more can reach the cap
-    counts = recs.numpy().reshape(nd, sb)[:, 40:48].copy().view("<i4")
-    may_not_converge = bool(((counts[:, 1] - counts[:, 0] + 1) >= jpeg_round_cap()).any())
+    heads = np.ascontiguousarray(recs.numpy().reshape(nd, sb)[:, :ctypes.sizeof(_lib.JpegScanHead)]).view(np.dtype(_lib.JpegScanHead))
+    may_not_converge = bool(((heads["nsub"] - heads["nseg"] + 1) >= jpeg_round_cap()).any())
     return JpegScanBatch(may_not_converge=may_not_converge, stream=stream, segs=segs, scans=recs, plans=plans, infos=infos, windows=windows, coef_bytes=co, nsub=no,
                          coef_offs=[o[0] for o in offs], offs=offs, out_offs=[o[2] for o in offs], out_end=oo,
                          dev_ids=dev_ids, host_ids=host_ids)
@@ -1501,7 +1499,7 @@ def jpeg_multiscan_decode(batch, datas, alloc=None, pool=None):
         plan = batch.plans[i * pb:(i + 1) * pb]
         jpeg_entropy_decode(datas[i], host[start:start + cb], (0, batch.offs[i][1], batch.offs[i][2]), plan, batch.windows[i], "any",
                             batch.infos[i])
-        plan[64:72].copy_(torch.tensor([off], dtype=torch.int64).view(torch.uint8))          # VtxJpegPlan.coef_off
+        _lib.JpegPlan.from_buffer(plan.numpy()).coef_off = off
 
     list(pool.map(job, spans) if pool is not None and len(spans) > 1 else map(job, spans))
     return host[:total], spans
