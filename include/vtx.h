@@ -787,6 +787,50 @@ int vtx_cls_metrics(const void* logits, const int64_t* labels, float* ce_rows, i
                     const int32_t* ks, int nk, const float* loss_override, float loss_scale, int B, int K,
                     int64_t ignore_index, int dtype, void* stream);
 
+/* ---- Weighted k-nearest-neighbour evaluation of frozen features (csrc/knn.hip, csrc/knn_select.h): the measure DINO
+ * runs are judged by.  The search streams the bank through LDS and never writes the (M, N) score matrix; the vote turns a
+ * query's neighbour list into the rank of its label.  No host synchronisation.
+ *
+ * vtx_knn_topk: q [M, D] queries, f [N, D] bank (both dtype, rows used as given -- nothing is normalised here),
+ *   val [M, k] fp32, idx [M, k] int32.
+ *   - Order.  The score of a pair is the fp32-accumulated dot product of its two rows.  Row m of the output holds the
+ *     first k bank rows in the total order "higher score first, among equal scores the lower bank index first" -- a STABLE
+ *     descending sort of the score row, the rule of vtx_cls_metrics -- listed in that order.  The order is total, so the
+ *     answer is unique.
+ *   - Pair-local scores.  The score of a pair depends on its two rows only (one MFMA chain over D for every pair): not
+ *     on M, N, the tile the pair falls in or splits.  The same pair gives the same bits in every call.
+ *   - splits: the bank is cut into `splits` (1..64; 0 = choose from M and N) slabs of consecutive rows; every slab
+ *     writes its own k-list to the workspace and a second launch merges them under the same order.  The answer does
+ *     not depend on splits.  Workspace: vtx_knn_workspace_bytes(M, N, k, splits) = 8 M splits k bytes (0 for one split),
+ *     4-byte aligned; ws may be NULL when that is 0.
+ *   - Non-finite scores give unspecified neighbours (a NaN score is treated as -inf); even then every returned index
+ *     lies in [0, N) and the call ends.
+ *   Errors, all before any launch: VTX_ERR_NULL (q, f, val, idx; ws when a workspace is needed), VTX_ERR_SHAPE (M < 1,
+ *   N < 1, M or N >= 2^31, D > 1024, k < 1, k > 256, k > N, splits outside 0..64), VTX_ERR_ALIGN (D % 8 != 0; q or f not
+ *   16-byte aligned), VTX_ERR_DTYPE, VTX_ERR_WORKSPACE (ws_bytes short).
+ *
+ * vtx_knn_vote: val / idx [M, L] (a search result, L <= 256), bank_labels [N] int64, query_labels [M] int64, ks: HOST
+ *   array of nk (1..8) values in 1..L, C classes, temperature T > 0.  Per query and per k in ks:
+ *     w_i      = expf(val_i / T) in fp32;
+ *     votes[c] = sum of w_i over the neighbours i < k whose bank label is c, added in neighbour order in fp32 (the vote
+ *                at a smaller k is a prefix of the vote at a larger one);
+ *     rank     = #{c : votes[c] > votes[l]} + #{c < l : votes[c] == votes[l]} over the classes [0, C), l the query's
+ *                label: its position in a STABLE descending sort of the votes.  Classes without a neighbour have vote 0
+ *                and take part in the tie rule.
+ *   rank [M, nk] int32; pred [M, nk] int32 = the class of rank 0.
+ *   Labels are compared, never used as indices: a bank label outside [0, C) votes for no class, a query label outside
+ *   [0, C) gives rank = C -- the row is counted and never a hit; an idx outside [0, N) is a neighbour of no class.
+ *   meter [1 + 2 nk] fp64 or NULL: [n, top1_ks0, top5_ks0, top1_ks1, top5_ks1, ...]; the call ADDS M and the rows with
+ *   rank < 1 and with rank < min(5, ks[i]).  One workgroup, fixed summation order, no atomics.
+ *   Errors: VTX_ERR_NULL (any pointer but meter), VTX_ERR_SHAPE (M, N < 1 or >= 2^31; L outside 1..256; C < 1; nk outside
+ *   1..8; ks[i] outside 1..L; T not > 0). */
+size_t vtx_knn_workspace_bytes(int64_t M, int64_t N, int k, int splits);
+int vtx_knn_topk(const void* q, const void* f, float* val, int32_t* idx, int64_t M, int64_t N, int D, int k, int splits,
+                 void* ws, size_t ws_bytes, int dtype, void* stream);
+int vtx_knn_vote(const float* val, const int32_t* idx, const int64_t* bank_labels, const int64_t* query_labels,
+                 int32_t* rank, int32_t* pred, double* meter, const int32_t* ks, int nk, int64_t M, int L, int64_t N, int C,
+                 float T, void* stream);
+
 /* ---- Multi-tensor weight cast (csrc/cast.hip): all fp32 Linear / Conv weights of a model -> bf16, plain [out][in]
  * and transposed [in][out], in one launch per forward.  This is the per-call weight cast of the reference's bf16
  * autocast (torch.cuda.amp.autocast around model(input), train.py:273-274) done once for the whole model.

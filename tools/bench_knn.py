@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""Micro-benchmark of the fused k-NN search (GPU box only): one box, one process, the two paths interleaved.
+
+Shapes: the ImageNet-1k bank of a ViT-S, N = 1 281 167 rows of D = 384 in bf16, M = 4096 queries, k = 20 and k = 200.
+  ours   vtx.knn.knn_search(q, bank, k)                      -- the score matrix never exists
+  torch  (q[i:i + 256] @ bank.T).topk(k) in chunks of 256    -- each chunk writes and re-reads 256 x N scores
+Per k: both times (GPU events around one whole search, best and median of --reps interleaved repetitions), their ratio,
+the achieved TFLOP/s of the search (2 M N D over its time) and the bank bytes per second (the bytes the query tiles pull
+through LDS: one pass over N D 2 bytes per query tile of 128 rows at k <= 64, of 64 rows above -- L2 / Infinity Cache
+traffic for all but the first pass of a slab).
+The two results are compared: same scores up to fp32 summation order, the same neighbour sets where no score ties within
+that.  The bar: ours is not slower than torch at either k.  --commit stamps the header, --out also writes the report."""
+import argparse
+import os
+import statistics
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "vision-transformers-pytorch_amd")):
+    sys.path.insert(0, p)
+import torch
+
+from vtx.knn import knn_search
+
+dev = torch.device("cuda")
+LINES = []
+
+
+def say(s):
+    print(s, flush=True)
+    LINES.append(s)
+
+
+def torch_search(q, bank, k, chunk=256):
+    vals, idxs = [], []
+    bt = bank.T
+    for i in range(0, q.shape[0], chunk):
+        v, j = (q[i:i + chunk] @ bt).topk(k, dim=1)
+        vals.append(v)
+        idxs.append(j)
+    return torch.cat(vals), torch.cat(idxs)
+
+
+def timed_ms(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    out = fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1), out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1_281_167)
+    ap.add_argument("--m", type=int, default=4096)
+    ap.add_argument("--d", type=int, default=384)
+    ap.add_argument("--ks", type=int, nargs="+", default=[20, 200])
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--splits", type=int, default=0)
+    ap.add_argument("--commit", default="unknown")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_knn.py measures on the GPU; there is no CPU path"
+
+    g = torch.Generator(device=dev).manual_seed(3)
+    bank = torch.nn.functional.normalize(torch.randn(a.n, a.d, device=dev, generator=g), dim=1).to(torch.bfloat16)
+    q = torch.nn.functional.normalize(torch.randn(a.m, a.d, device=dev, generator=g), dim=1).to(torch.bfloat16)
+    say(f"# k-NN search microbench, commit {a.commit}: N = {a.n}, D = {a.d} bf16, M = {a.m}, {torch.cuda.get_device_name(0)}, "
+        f"{a.reps} interleaved repetitions")
+    flop = 2.0 * a.m * a.n * a.d
+    for k in a.ks:
+        tile = 128 if k <= 64 and a.m > 64 else 64                     # knn_tile_rows of csrc/knn.hip
+        passes = (a.m + tile - 1) // tile
+        ours = lambda: knn_search(q, bank, k, a.splits)
+        ref = lambda: torch_search(q, bank, k)
+        (_, (v, i)), (_, (tv, ti)) = timed_ms(ours), timed_ms(ref)          # warm-up of both, and the comparison
+        dv = (v - tv.float()).abs().max().item()
+        same = (i.long().sort(dim=1).values == ti.sort(dim=1).values).all(dim=1).float().mean().item()
+        del v, i, tv, ti
+        t_ours, t_ref = [], []
+        for _ in range(a.reps):
+            t_ours.append(timed_ms(ours)[0])
+            t_ref.append(timed_ms(ref)[0])
+        bo, br = min(t_ours), min(t_ref)
+        mo, mr = statistics.median(t_ours), statistics.median(t_ref)
+        say(f"k = {k:3d}: fused search best {bo:8.2f} ms, median {mo:8.2f} ms | torch mm + topk (chunks of 256) best {br:8.2f} ms, "
+            f"median {mr:8.2f} ms | torch / fused = {mr / mo:5.2f}x (median)")
+        say(f"         fused: {flop / mo / 1e9:7.1f} TFLOP/s, bank bytes through LDS {passes * a.n * a.d * 2 / mo / 1e9:7.2f} TB/s "
+            f"({passes} passes over {a.n * a.d * 2 / 1e6:.0f} MB) | max |val - torch val| {dv:.2e}, rows with the same "
+            f"neighbour set {100 * same:.2f} % (torch's mm rounds its scores to bf16 before the topk)")
+        say(f"         bar (fused not slower than torch): {'MET' if mo <= mr else 'MISSED'}")
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write("\n".join(LINES) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -7,7 +7,11 @@
   vtx.tables      integer window tables (pos / local_mask), bit-exact vs the reference
   vtx.ddp         data-parallel gradient all-reduce over RCCL on a side stream
   vtx.optim       FusedAdamW (clip + AdamW + model EMA in one pass), ModelEma; vtx.accumulate = train_util.accumulate
+  vtx.knn         weighted k-NN evaluation of frozen features: FeatureBank, knn_search, KnnMeter, extract_features,
+                  knn_evaluate (also reachable as vtx.FeatureBank, ...)
 """
+
+_KNN_NAMES = ("FeatureBank", "KnnMeter", "knn_search", "extract_features", "knn_evaluate")
 
 
 def __getattr__(name):
@@ -16,4 +20,7 @@ def __getattr__(name):
     if name == "accumulate":
         from .optim import accumulate
         return accumulate
+    if name in _KNN_NAMES:
+        from . import knn
+        return getattr(knn, name)
     raise AttributeError(f"module 'vtx' has no attribute {name!r}")

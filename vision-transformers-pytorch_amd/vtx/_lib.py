@@ -269,6 +269,11 @@ _SIGNATURES = {
                              c_int, c_void_p]),
     "vtx_cls_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float, c_int,
                                 c_int, c_int64, c_int, c_void_p]),
+    "vtx_knn_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
+    "vtx_knn_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p,
+                             c_size_t, c_int, c_void_p]),
+    "vtx_knn_vote": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                             c_int64, c_int, c_int64, c_int, c_float, c_void_p]),
     "vtx_cast_desc_bytes": (c_size_t, []),
     "vtx_cast_weights": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vtx_patch_gather": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -1715,6 +1715,57 @@ def l2norm_bwd(dy, y, nrm, eps=1e-12):
     return dx
 
 
+def knn_workspace_bytes(M, N, k, splits=0):
+    """Bytes of workspace vtx_knn_topk needs for M queries against N bank rows (0 when one split is used)."""
+    return int(_lib.load().vtx_knn_workspace_bytes(int(M), int(N), int(k), int(splits)))
+
+
+def knn_topk(q, f, k, splits=0):
+    """The k bank rows of ``f`` (N, D) with the highest dot product for every row of ``q`` (M, D), both float32 or both
+    bfloat16, in the total order "higher score first, lower bank index first"; the score matrix is never written.
+    ``splits``: slabs of the bank searched by separate workgroups (0 = choose); the answer does not depend on it.
+    -> (val fp32 [M, k], idx int32 [M, k]); limits: include/vtx.h."""
+    _dev(q, f)
+    if q.dim() != 2 or f.dim() != 2 or q.shape[1] != f.shape[1] or q.dtype != f.dtype:
+        raise VtxError(f"vtx: knn_topk takes (M, D) queries and an (N, D) bank of one dtype, got {tuple(q.shape)} {q.dtype} / "
+                       f"{tuple(f.shape)} {f.dtype}")
+    M, D = q.shape
+    N = f.shape[0]
+    val = torch.empty((M, int(k)), dtype=torch.float32, device=q.device)
+    idx = torch.empty((M, int(k)), dtype=torch.int32, device=q.device)
+    lib = _lib.load()
+    nws = int(lib.vtx_knn_workspace_bytes(M, N, int(k), int(splits)))
+    ws = torch.empty(nws, dtype=torch.uint8, device=q.device) if nws else None
+    with _timed("knn_search_kernel", 2.0 * M * N * D, float(N) * D * f.element_size()):
+        check(lib.vtx_knn_topk(_p(q), _p(f), _p(val), _p(idx), M, N, D, int(k), int(splits), _p(ws), nws, _dt(q), _stream()),
+              "vtx_knn_topk")
+    return val, idx
+
+
+def knn_vote(val, idx, bank_labels, query_labels, ks, n_class, T, meter=None):
+    """Weighted vote of a search result: w = expf(val / T), votes per class in neighbour order, the rank of every query's
+    label and the winning class for each k of ``ks`` (ints or a prepared ``ctypes.c_int32`` array); with ``meter`` (float64
+    device tensor [n, top1, top5, ...] of 1 + 2 len(ks) values) the batch is added to it in the same call.
+    -> (rank int32 [M, nk], pred int32 [M, nk]); rules: include/vtx.h."""
+    _dev(val, idx, bank_labels, query_labels, meter)
+    if val.dim() != 2 or val.shape != idx.shape or val.dtype != torch.float32 or idx.dtype != torch.int32:
+        raise VtxError("vtx: knn_vote takes the (val fp32, idx int32) pair of knn_topk")
+    M, L = val.shape
+    if query_labels.numel() != M or bank_labels.dim() != 1:
+        raise VtxError(f"vtx: knn_vote needs {M} query labels and a 1-D bank label tensor")
+    bl = bank_labels if bank_labels.dtype == torch.int64 else bank_labels.to(torch.int64)
+    ql = query_labels if query_labels.dtype == torch.int64 else query_labels.to(torch.int64)
+    nk = len(ks)
+    kk = ks if isinstance(ks, ctypes.Array) else (ctypes.c_int32 * nk)(*[int(k) for k in ks])
+    if meter is not None and (meter.dtype != torch.float64 or meter.numel() != 1 + 2 * nk):
+        raise VtxError(f"vtx: the k-NN meter is a float64 tensor of 1 + 2 * {nk} values")
+    rank = torch.empty((M, nk), dtype=torch.int32, device=val.device)
+    pred = torch.empty((M, nk), dtype=torch.int32, device=val.device)
+    check(_lib.load().vtx_knn_vote(_p(val), _p(idx), _p(bl), _p(ql), _p(rank), _p(pred), _p(meter), kk, nk, M, L,
+                                   bl.numel(), int(n_class), float(T), _stream()), "vtx_knn_vote")
+    return rank, pred
+
+
 # ------------------------------------------------------------------------------- data movement
 def cast_desc_bytes():
     return _lib.load().vtx_cast_desc_bytes()
