@@ -463,6 +463,31 @@ int vtx_xattn_bwd_drop(const void* q, const void* kv, const void* o, const void*
                        void* dkv, float* dbias, void* workspace, size_t ws_bytes, int B, int Lq, int Lk, int nH, int D, int dtype,
                        float drop_p, uint64_t seed, const uint8_t* keep, void* stream);
 
+/* ---- Global attention for any head width (csrc/attention_hd.hip): softmax(q k^T / sqrt(D)) v with D ANY MULTIPLE OF 8 IN 8..128 -- the
+ * global-attention families only (ViT / DINO, PVT, the Twins global half; reference models/vit.py:20, pvt.py:12-30, twins.py:39-93 take
+ * any dim // n_head).  Window attention (Swin, Twins local) keeps its 32 | 64 rule, halo attention its 32 | 64 with a bias: no bias and
+ * no mask here.  D = 32 and 64 are accepted too; the models only come here where the entries above refuse (D not in {32, 64}, or
+ * vtx_attention_* at D = 32 with 160 < L <= 224).
+ *   q [B * Lq, nH * D] with row stride ldq, k and v [B * Lk, nH * D] with row stride ldkv (elements): three pointers, so the packed
+ *   QKV projection (k = q + nH D, v = q + 2 nH D, Lq = Lk, ldq = ldkv = 3 nH D) and the q | kv pair of the sub-sampled attention
+ *   (ldq = nH D, v = k + nH D, ldkv = 2 nH D) are both served;  o, dout [B * Lq, nH * D] contiguous;  lse [B * nH * Lq] fp32;
+ *   dq (row stride lddq), dk, dv (row stride lddkv): every element of the nH * D gradient columns is written.
+ *   drop_p == 0: no dropout (keep must be NULL);  0 < drop_p < 1: dropout of the probabilities as vtx_attention_fwd_drop, problem =
+ *   image * nH + head, cell = query * Lk + key -- vtx_attn_keep_mask exports the decisions; keep != NULL: an explicit mask of
+ *   keep_cells = B * nH * Lq * Lk bytes.  A query row whose keys are all dropped stores exact zeros in o and dq.
+ * Kernels templated on the padded width 32 | 64 | 96 | 128; pad columns are zero operands that are never loaded and never stored.
+ * Refused before any launch: NULL pointers (VTX_ERR_NULL); D % 8 != 0, D < 8, D > 128, non-positive sizes, B * Lq or B * Lk >= 2^31,
+ * a stride below nH * D, keep_cells != B * nH * Lq * Lk, drop_p outside [0, 1) (VTX_ERR_SHAPE); dtypes other than bf16 / fp32
+ * (VTX_ERR_DTYPE); strides that are no multiple of 8 or bases off 16 bytes (VTX_ERR_ALIGN); ws_bytes below
+ * vtx_attn_hd_bwd_workspace (VTX_ERR_WORKSPACE). */
+int vtx_attn_hd_fwd(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldkv, void* o, float* lse, int B, int Lq, int Lk,
+                    int nH, int D, int dtype, float drop_p, uint64_t seed, const uint8_t* keep, int64_t keep_cells, void* stream);
+size_t vtx_attn_hd_bwd_workspace(int B, int Lq, int nH);
+int vtx_attn_hd_bwd(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldkv, const void* o, const void* dout,
+                    const float* lse, void* dq, void* dk, void* dv, int64_t lddq, int64_t lddkv, void* workspace, size_t ws_bytes, int B,
+                    int Lq, int Lk, int nH, int D, int dtype, float drop_p, uint64_t seed, const uint8_t* keep, int64_t keep_cells,
+                    void* stream);
+
 /* ---- Positional-encoding generator of Twins-SVT (csrc/twins_misc.hip; reference models/twins.py:25-37):
  * y = x + DepthwiseConv3x3(x) on channels-last features x, y [B, H, W, C] (C % 8 == 0, C <= 1024), w = the
  * Conv2d(C, C, 3, padding=1, bias=False, groups=C) weight [C, 1, 3, 3] fp32.  The reference permutes to NCHW, convolves and

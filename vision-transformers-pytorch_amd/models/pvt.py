@@ -43,7 +43,11 @@ class MultiHeadedAttention(nn.Module):
         """True when F.dropout(attn, self.dropout, self.training) of the reference (pvt.py:60) is active."""
         return self.training and self.dropout > 0
 
-    def forward(self, input, height, width, prev=None, keep=None):
+    def generic_width(self):
+        """True for the head widths only csrc/attention_hd.hip serves (not 32 / 64): the layer then runs call by call."""
+        return self.dim_head not in (32, 64)
+
+    def forward(self, input, height, width, prev=None, keep=None, want_score=True):
         """The reference's standalone contract (models/pvt.py:31-69): input (B, L, dim) with the last height * width tokens
         on the grid (leading tokens -- a cls token -- attend but are not reduced); returns ``(out, score)`` with score =
         q k^T / sqrt(d) of shape (B, heads, L, Lk) before the softmax.  The PVT layers do not come through here (they run
@@ -71,14 +75,35 @@ class MultiHeadedAttention(nn.Module):
         q2 = q.reshape(B * L, C)
         out = VF.SrAttentionFn.apply(q2, kv, B, L, Lk, self.n_head, VF.attn_drop(self.dropout, self.training, keep))
         out = VF.LinearFn.apply(out.view(B, L, C), self.linear.weight, self.linear.bias)
+        if not want_score:                                  # (pvt.TransformerLayer discards it: nothing is computed)
+            return out, None
         from vtx import ops
         with torch.no_grad():
-            score = ops.srattn_scores(q2.detach().contiguous(), kv.detach().contiguous(), B, L, Lk, self.n_head)
+            qd, kvd = q2.detach().contiguous(), kv.detach().contiguous()
+            if self.generic_width():
+                # q k^T / sqrt(d) per (image, head) from the two projections with the GEMM entry: the head's columns are copied
+                # out (the entry takes dense operands), the keys padded with zero rows to the entry's 8-column granularity, and
+                # the 1 / sqrt(d) rides in the row-scale epilogue.  Inference-side helper, no gradient.
+                D, nH = self.dim_head, self.n_head
+                Lk8 = (Lk + 7) // 8 * 8
+                qh = qd.view(B, L, nH, D).permute(0, 2, 1, 3).contiguous()
+                kh = torch.zeros((B, nH, Lk8, D), dtype=kvd.dtype, device=kvd.device)
+                kh[:, :, :Lk] = kvd.view(B, Lk, 2, nH, D)[:, :, 0].permute(0, 2, 1, 3)
+                scale = torch.full((1,), 1.0 / math.sqrt(D), dtype=torch.float32, device=qd.device)
+                full = torch.empty((B, nH, L, Lk8), dtype=qd.dtype, device=qd.device)
+                for b in range(B):
+                    for h in range(nH):
+                        ops.gemm(qh[b, h], kh[b, h], 0, rowscale=scale, rows_per_scale=L, out=full[b, h])
+                score = full[..., :Lk].contiguous()
+            else:
+                score = ops.srattn_scores(qd, kvd, B, L, Lk, self.n_head)
         return out, score
 
     def check(self):
-        if self.dim_head != 64:
-            raise NotImplementedError("vtx: the PVT attention kernel is built for head dim 64 (all PVT configurations)")
+        from vtx import ops
+        if self.dim_head * self.n_head != self.linear_q.weight.shape[0] or not ops.attn_hd_supported(self.dim_head):
+            raise NotImplementedError(f"vtx: PVT attention needs dim = heads x head dim with a head dim that is a multiple of 8 in "
+                                      f"8..128 (got head dim {self.dim_head})")
 
 
 class TransformerLayer(nn.Module):
@@ -96,9 +121,10 @@ class TransformerLayer(nn.Module):
     def forward(self, input, height, width):
         a, f = self.attn, self.ff
         a.check()
-        if a.drops():
-            # attention dropout: call by call (pvt.py:99-103) through the standalone module (its score output is discarded)
-            out = input + self.drop_path(a(self.norm_attn(input), height, width)[0])
+        if a.drops() or a.generic_width():
+            # attention dropout, or a head width other than 32 / 64: call by call (pvt.py:99-103) through the standalone module
+            # (its score output is discarded, so it is not computed)
+            out = input + self.drop_path(a(self.norm_attn(input), height, width, want_score=False)[0])
             return out + self.drop_path(f(self.norm_ff(out)))
         if not f.fused_ok():
             raise NotImplementedError("vtx: PVT runs on the fused layer only (SiLU activation, dropout 0)")

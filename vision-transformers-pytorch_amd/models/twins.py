@@ -71,8 +71,9 @@ class MultiHeadedAttention(nn.Module):
 
     def check(self, height, width):
         r = self.reduction
-        if self.dim_head not in (32, 64):
-            raise NotImplementedError("vtx: the sub-sampled attention kernel is built for head dim 32 or 64")
+        if self.dim_head * self.n_head != self.linear_q.weight.shape[0] or not VF.ops.attn_hd_supported(self.dim_head):
+            raise NotImplementedError(f"vtx: the sub-sampled attention needs dim = heads x head dim with a head dim that is a multiple "
+                                      f"of 8 in 8..128 (got head dim {self.dim_head})")
         if r <= 1:
             # reference twins.py:74-77 would chunk its 4-D (B, H, W, 2 dim) projection along dim 2 (the width) in that case;
             # TransformerLayer never builds the module that way (reduction = window_size, twins.py:182)
@@ -175,7 +176,8 @@ class TransformerLayer(nn.Module):
         self.drop_path.p = p
 
     def forward(self, input):
-        if not (self.ff_local.fused_ok() and self.ff_global.fused_ok()) or self.attn_local.drops() or self.attn_global.drops():
+        if (not (self.ff_local.fused_ok() and self.ff_global.fused_ok()) or self.attn_local.drops() or self.attn_global.drops()
+                or self.attn_global.dim_head not in (32, 64)):          # (global head widths of csrc/attention_hd.hip: call by call)
             out = input + self.drop_path(self.attn_local(self.norm_attn_local(input)))
             out = out + self.drop_path(self.ff_local(self.norm_ff_local(out)))
             out = out + self.drop_path(self.attn_global(self.norm_attn_global(out)))

@@ -44,6 +44,11 @@ class MultiHeadedAttention(nn.Module):
         self.linear = Linear(dim, dim)
 
     def meta(self, length, eps=1e-6):
+        # any head width that is a multiple of 8 up to 128 (64 and, up to 160 / beyond 224 tokens, 32 on the register-resident and
+        # key-block kernels; everything else on csrc/attention_hd.hip)
+        if self.dim_head * self.n_head * 3 != self.qkv.weight.shape[0] or not VF.ops.attn_hd_supported(self.dim_head):
+            raise NotImplementedError(f"vtx: ViT attention needs dim = heads x head dim with a head dim that is a multiple of 8 in "
+                                      f"8..128 (got dim {self.qkv.weight.shape[1]}, {self.n_head} heads: head dim {self.dim_head})")
         return VF.AttentionMeta(self.n_head, self.dim_head, length, eps=eps)
 
     def drops(self):

@@ -404,6 +404,8 @@ def _layer_kind(x, rel_pos, meta):
         return 0
     if _wattn_ok(rel_pos, meta):
         return _lib.ATTN_WINDOW
+    if _attn_hd(rel_pos, meta):
+        return 0                             # (head widths of csrc/attention_hd.hip: call by call, no one-call layer)
     if rel_pos is None and meta.swin is None and meta.mask is None and meta.csr is None:
         return _lib.ATTN_GLOBAL
     return 0
@@ -691,9 +693,17 @@ def attn_drop(p, training, keep=None):
     return (float(p), seed, keep)
 
 
+def _attn_hd(rel_pos, meta):
+    """Global attention (no window, no rel_pos, no mask) at a head width / length the 32 | 64 kernels refuse: vtx_attn_hd_*."""
+    return ops.attn_hd_routes(meta.dim_head, meta.L, swin=meta.swin is not None, bias=rel_pos is not None, mask=meta.mask is not None)
+
+
 def _attn_forward(qkv, rel_pos, meta, drop=None):
     """-> (o, lse, aux) where aux is what the matching backward needs (the bias tensor of the generic path)."""
     B = qkv.shape[0]
+    if _attn_hd(rel_pos, meta):
+        o, lse = ops.attn_hd_fwd(qkv, None, B, meta.L, meta.L, meta.n_head, meta.dim_head, drop=drop)
+        return o.view(qkv.shape[:-1] + (meta.n_head * meta.dim_head,)), lse, None
     if drop is None and _wattn_ok(rel_pos, meta):
         o, lse = ops.wattn_fwd(qkv, rel_pos.detach(), meta.pos, meta.region, B, meta.L, meta.n_head, meta.swin)
         return o, lse, None
@@ -706,6 +716,8 @@ def _attn_backward(qkv, o, do, lse, aux, meta, rel_pos=None, defer=False, drop=N
     """-> dqkv, drel_pos (an ops.Partials with ``defer`` on the window-attention fast path: reduced later in one launch
     with the layer's LayerNorm partials)."""
     B = qkv.shape[0]
+    if _attn_hd(rel_pos, meta):
+        return ops.attn_hd_bwd(qkv, None, o, do, lse, B, meta.L, meta.L, meta.n_head, meta.dim_head, drop=drop), None
     if drop is None and _wattn_ok(rel_pos, meta):
         return ops.wattn_bwd(qkv, o, do, lse, rel_pos.detach(), meta.pos, meta.region, B, meta.L, meta.n_head,
                              meta.swin, meta.ntab, defer=defer)
@@ -1161,7 +1173,13 @@ class SrAttentionFn(Function):
     @staticmethod
     def forward(ctx, q, kv, B, Lq, Lk, n_head, drop=None):
         q, kv = _c(q), _c(kv)
-        o, lse = ops.srattn_fwd(q, kv, B, Lq, Lk, n_head, drop=drop)
+        D = q.shape[-1] // n_head
+        ctx.hd = D if ops.attn_hd_routes(D) else 0          # widths other than 32 / 64: csrc/attention_hd.hip, at any Lk
+        if ctx.hd:
+            o, lse = ops.attn_hd_fwd(q, kv, B, Lq, Lk, n_head, D, drop=drop)
+            o = o.view(q.shape)
+        else:
+            o, lse = ops.srattn_fwd(q, kv, B, Lq, Lk, n_head, drop=drop)
         ctx.save_for_backward(q, kv, o, lse)
         ctx.geom, ctx.drop = (B, Lq, Lk, n_head), drop
         return o
@@ -1170,7 +1188,10 @@ class SrAttentionFn(Function):
     def backward(ctx, do):
         side_fence(do.device)
         q, kv, o, lse = ctx.saved_tensors
-        dq, dkv = ops.srattn_bwd(q, kv, o, _c(do), lse, *ctx.geom, drop=ctx.drop)
+        if ctx.hd:
+            dq, dkv = ops.attn_hd_bwd(q, kv, o, _c(do), lse, *ctx.geom, ctx.hd, drop=ctx.drop)
+        else:
+            dq, dkv = ops.srattn_bwd(q, kv, o, _c(do), lse, *ctx.geom, drop=ctx.drop)
         return dq, dkv, None, None, None, None, None
 
 

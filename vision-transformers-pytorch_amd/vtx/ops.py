@@ -832,6 +832,103 @@ def xattn_bwd(q, kv, o, dout, lse, B, Lq, Lk, n_head, bias=None, drop=None):
     return dq, dkv, dbias
 
 
+# ------------------------------------------------------------------------------- global attention at any head width (csrc/attention_hd.hip)
+def attn_hd_supported(D):
+    """Head widths of vtx_attn_hd_*: the multiples of 8 in 8..128."""
+    return isinstance(D, int) and 8 <= D <= 128 and D % 8 == 0
+
+
+def attn_hd_pad(D):
+    """Padded width the kernels are instantiated on (pad columns are zero operands that are never loaded)."""
+    return 32 if D <= 32 else (64 if D <= 64 else (96 if D <= 96 else 128))
+
+
+def attn_hd_routes(D, L=None, swin=False, bias=False, mask=False):
+    """True where a GLOBAL attention call (no window, no rel_pos / bias, no mask) goes to vtx_attn_hd_*: exactly where the entries
+    that served it so far refuse -- head widths other than 32 / 64, and 32 between 161 and 224 tokens on the packed-QKV entry
+    (ATTN_DISPATCH ends at 160, the key-block kernels start at 225).  ``L=None``: the q | kv (sub-sampled) entry, whose 32 / 64 kernels
+    take any length.  Everything else keeps the kernel it has (or its refusal: widths vtx_attn_hd_* does not take either)."""
+    if swin or bias or mask or not attn_hd_supported(D):
+        return False
+    if D not in (32, 64):
+        return True
+    return D == 32 and L is not None and 160 < L <= 224
+
+
+def _attn_hd_views(q, kv, B, Lq, Lk, n_head, D):
+    """(q, k, v) 2-D column views + (ldq, ldkv) of the packed QKV projection (kv None) or the q | kv pair."""
+    if not attn_hd_supported(D):
+        raise VtxError(f"vtx: head dim {D} -- global attention takes the multiples of 8 in 8..128")
+    hd = n_head * D
+    if kv is None:
+        _dev(q)
+        if Lq != Lk or q.numel() != B * Lq * 3 * hd:
+            raise VtxError(f"vtx: attn_hd shape mismatch (qkv {tuple(q.shape)}, {n_head} heads of {D}, {B} x {Lq} tokens)")
+        t = q.view(B * Lq, 3 * hd)
+        return t[:, :hd], t[:, hd:2 * hd], t[:, 2 * hd:], 3 * hd, 3 * hd
+    _dev(q, kv)
+    if q.dtype != kv.dtype or q.numel() != B * Lq * hd or kv.numel() != B * Lk * 2 * hd:
+        raise VtxError(f"vtx: attn_hd shape mismatch (q {tuple(q.shape)}, kv {tuple(kv.shape)}, {n_head} heads of {D})")
+    t = kv.view(B * Lk, 2 * hd)
+    return q.view(B * Lq, hd), t[:, :hd], t[:, hd:], hd, 2 * hd
+
+
+def _attn_hd_drop(drop, dev, cells):
+    if drop is None:
+        return 0.0, 0, None, 0
+    dp, seed, keep = _drop_args(drop, dev, cells)
+    return dp, seed, keep, (cells if keep is not None else 0)
+
+
+def attn_hd_fwd(q, kv, B, Lq, Lk, n_head, D, drop=None):
+    """o [B*Lq, h*D], lse [B*h*Lq] = softmax(q k^T / sqrt(D)) v at any head width D % 8 == 0, 8 <= D <= 128 (no bias, no mask).
+    kv None: q is the packed QKV projection [B*L, 3*h*D] (Lq == Lk); else q [B*Lq, h*D] and kv [B*Lk, 2*h*D] (k | v).
+    drop = (p, seed, keep): dropout of the probabilities; keep uint8 [B*h, Lq, Lk] replaces the hash."""
+    qv, kk, vv, ldq, ldkv = _attn_hd_views(q, kv, B, Lq, Lk, n_head, D)
+    hd = n_head * D
+    o = torch.empty((B * Lq, hd), dtype=q.dtype, device=q.device)
+    lse = torch.empty(B * n_head * Lq, dtype=torch.float32, device=q.device)
+    tn = "__bf16" if q.dtype == torch.bfloat16 else "float"
+    ev = _attn_bracket(f"hdattn_fwd_kernel<{tn}, {attn_hd_pad(D)}>", B * n_head, Lq, D, B * Lq, hd, q.element_size(), False)
+    if ev is not None:                              # Lq x Lk products on the unpadded width
+        _timer.records[-1] = (_timer.records[-1][0], 4.0 * B * n_head * Lq * Lk * D,
+                              q.element_size() * (2.0 * B * Lq * hd + 2.0 * B * Lk * hd)) + _timer.records[-1][3:]
+    dp, seed, keep, cells = _attn_hd_drop(drop, q.device, B * n_head * Lq * Lk)
+    check(_lib.load().vtx_attn_hd_fwd(_p(qv), _p(kk), _p(vv), ldq, ldkv, _p(o), _p(lse), B, Lq, Lk, n_head, D, _dt(q), dp, seed,
+                                      _p(keep), cells, _stream()), "vtx_attn_hd_fwd")
+    if ev:
+        ev[1].record()
+    return o, lse
+
+
+def attn_hd_bwd(q, kv, o, dout, lse, B, Lq, Lk, n_head, D, drop=None):
+    """-> dqkv (packed layout, kv None) or (dq, dkv): every element written, deterministic; drop: the forward's (p, seed, keep)."""
+    qv, kk, vv, ldq, ldkv = _attn_hd_views(q, kv, B, Lq, Lk, n_head, D)
+    _dev(o, dout, lse)
+    _f32(lse, "lse")
+    hd = n_head * D
+    if o.dtype != q.dtype or dout.dtype != q.dtype or o.numel() != B * Lq * hd or dout.numel() != B * Lq * hd or \
+            lse.numel() != B * n_head * Lq:
+        raise VtxError("vtx: attn_hd backward operands do not match the forward's (o, dout [B*Lq, h*D] of q's dtype, lse [B*h*Lq])")
+    lib = _lib.load()
+    dq = torch.empty_like(q)
+    dkv = torch.empty_like(kv) if kv is not None else None
+    dqv, dkk, dvv, _, _ = _attn_hd_views(dq, dkv, B, Lq, Lk, n_head, D)
+    wsb = lib.vtx_attn_hd_bwd_workspace(B, Lq, n_head)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
+    tn = "__bf16" if q.dtype == torch.bfloat16 else "float"
+    ev = _attn_bracket(f"hdattn_bwd_*_kernel<{tn}, {attn_hd_pad(D)}>", B * n_head, Lq, D, B * Lq, hd, q.element_size(), True)
+    if ev is not None:
+        _timer.records[-1] = (_timer.records[-1][0], 10.0 * B * n_head * Lq * Lk * D,
+                              q.element_size() * (4.0 * B * Lq * hd + 4.0 * B * Lk * hd)) + _timer.records[-1][3:]
+    dp, seed, keep, cells = _attn_hd_drop(drop, q.device, B * n_head * Lq * Lk)
+    check(lib.vtx_attn_hd_bwd(_p(qv), _p(kk), _p(vv), ldq, ldkv, _p(o), _p(dout), _p(lse), _p(dqv), _p(dkk), _p(dvv), ldq, ldkv,
+                              _p(ws), wsb, B, Lq, Lk, n_head, D, _dt(q), dp, seed, _p(keep), cells, _stream()), "vtx_attn_hd_bwd")
+    if ev:
+        ev[1].record()
+    return dq if kv is None else (dq, dkv)
+
+
 def dwconv3_fwd(x, w, adjoint=False):
     """y = x + DepthwiseConv3x3(x) on channels-last x (B, H, W, C), w (C, 1, 3, 3) fp32 -- twins.py:25-37; adjoint: the input
     gradient of the same map (x := dy)."""
