@@ -5,7 +5,8 @@ column bias, one sample's DropPath scale.  ``check_elementwise`` asserts |got - 
 never a measured number: each builder below computes it in fp64 from the arithmetic its kernel is documented to do, with
 absolute-value products, and carries its derivation.  tests/test_elementwise_host.py proves every builder on the CPU (a torch
 model of a correct kernel has zero violations; planted defects are found and located); tests/test_gpu_elementwise.py and
-tests/test_gpu_attn_drop_elementwise.py (attention dropout, the generic window path) run the kernels against them.
+tests/test_gpu_attn_drop_elementwise.py (attention dropout, the generic window path) run the kernels against them;
+tests/test_gpu_layer_elementwise.py runs their row-mapped instances, launch by launch through a compacted one-call layer.
 
 Conventions, stated once:
   U32 = 2^-24   unit roundoff of an fp32 operation (every accumulator, every epilogue expression)

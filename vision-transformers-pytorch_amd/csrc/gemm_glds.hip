@@ -561,6 +561,7 @@ int gemm_glds_launch_mapped(const GemmArgs& a, hipStream_t st) {
   if (a.N % 128 != 0 || a.K % 64 != 0 || vtx_opt(VTX_OPT_GLDS_EPI) != 1) return VTX_ERR_SHAPE;   // wave-private epilogue kernels only
   if (a.rowscale != nullptr && a.rows_per_scale != a.map_T) return VTX_ERR_SHAPE;
   if (3 * a.map_T < 126) return VTX_ERR_SHAPE;                      // TileRowMap: a 128-row tile spans at most four samples
+  if ((uint64_t)a.M * (uint64_t)a.map_T >= 0x100000000ull) return VTX_ERR_SHAPE;   // row / T by __umulhi is exact below 2^32 / T (as the mapped LayerNorm)
   if (a.Mk < a.M && a.resid == nullptr) return VTX_ERR_SHAPE;       // copy-only rows need something to copy
   if (gemm_pp_ok(a)) return gemm_pp_launch(a, st);
   if (gemm_astat_ok(a)) return gemm_astat_launch(a, st);
