@@ -465,8 +465,8 @@ int vtx_xattn_bwd_drop(const void* q, const void* kv, const void* o, const void*
 
 /* ---- Global attention for any head width (csrc/attention_hd.hip): softmax(q k^T / sqrt(D)) v with D ANY MULTIPLE OF 8 IN 8..128 -- the
  * global-attention families only (ViT / DINO, PVT, the Twins global half; reference models/vit.py:20, pvt.py:12-30, twins.py:39-93 take
- * any dim // n_head).  Window attention (Swin, Twins local) keeps its 32 | 64 rule, halo attention its 32 | 64 with a bias: no bias and
- * no mask here.  D = 32 and 64 are accepted too; the models only come here where the entries above refuse (D not in {32, 64}, or
+ * any dim // n_head).  No bias and no mask in these three entries: window and halo attention at any head width are vtx_attn_hdw_*
+ * below, the same kernels with a bias, a mask and window addressing.  D = 32 and 64 are accepted too; the models only come here where the entries above refuse (D not in {32, 64}, or
  * vtx_attention_* at D = 32 with 160 < L <= 224).
  *   q [B * Lq, nH * D] with row stride ldq, k and v [B * Lk, nH * D] with row stride ldkv (elements): three pointers, so the packed
  *   QKV projection (k = q + nH D, v = q + 2 nH D, Lq = Lk, ldq = ldkv = 3 nH D) and the q | kv pair of the sub-sampled attention
@@ -487,6 +487,36 @@ int vtx_attn_hd_bwd(const void* q, const void* k, const void* v, int64_t ldq, in
                     const float* lse, void* dq, void* dk, void* dv, int64_t lddq, int64_t lddkv, void* workspace, size_t ws_bytes, int B,
                     int Lq, int Lk, int nH, int D, int dtype, float drop_p, uint64_t seed, const uint8_t* keep, int64_t keep_cells,
                     void* stream);
+
+/* ---- Window and halo attention for any head width and any window (csrc/attention_hd.hip, the WX instantiations): the kernels of
+ * vtx_attn_hd_* with an additive score bias, a byte mask and window addressing -- Swin, the Twins locally-grouped half and Halo at
+ * every D that is a multiple of 8 in 8..128 and every window size (blocks of 64 keys: no token limit).  The reference's modules take any
+ * dim_head (swin_transformer.py:25-40, twins.py:109-157, halo_transformer.py:23-30; HaloNet's usual width is 16).
+ *   q, k, v, ldq, ldkv, o, dout, dq, dk, dv, lddq, lddkv, drop_p, seed, keep, keep_cells: as vtx_attn_hd_*.
+ *   win > 0: B counts IMAGES; token t of window n of image b is a row of the (H, W) NHWC map, shift != 0 selects the rolled partition (the
+ *            roll by -win/2 and back folded into the address: what vtx_attention_fwd does with swin != 0).  q / k / v are read and o,
+ *            dq, dk, dv written in map order; no partition pass.  Lq == Lk == win * win; problems = B * nW, nW = (H / win) (W / win).
+ *   win == 0: B problems of plain rows b * L + t (the gathered q | kv pair of halo attention); H, W, shift are ignored.
+ *   bias  fp32 [nH][Lq][Lk] or NULL: added to scale * q.k in fp32 before the online softmax, and again where the backward recomputes P.
+ *   mask  uint8 [nW][Lq][Lk] or NULL (win > 0 only): a nonzero byte makes the score -inf; problem (b, n) reads mask[n].  A masked cell
+ *         has p = 0 and dS = 0 exactly.  PRECONDITION: every query row has at least one unmasked key (true of every local_mask the
+ *         reference builds: a token lies in its own region).  A key block that is fully masked for a query is fine.
+ *   lse   [problems * nH * Lq] in the order (problem, head, query).  Dropout problem index = (image * nW + window) * nH + head, as
+ *         vtx_attention_fwd_drop; keep_cells = problems * nH * Lq * Lk.
+ *   dbias fp32 [nH][Lq][Lk] = the sum of dS over all problems, given exactly when bias is: the problems are cut into slabs, each slab
+ *         summed in problem order into the workspace and the slabs added in slab order (deterministic, no atomics).  The table
+ *         gradient follows with vtx_table_bias_bwd.
+ * Refusals, before any launch: those of vtx_attn_hd_* with the same codes, and VTX_ERR_SHAPE for win < 0, H or W no multiple of win,
+ * Lq != win * win or Lk != Lq with win > 0, a mask with win == 0, bias without dbias or dbias without bias in the backward;
+ * VTX_ERR_WORKSPACE for ws_bytes below vtx_attn_hdw_bwd_workspace(.., has_bias). */
+int vtx_attn_hdw_fwd(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldkv, void* o, float* lse, const float* bias,
+                     const uint8_t* mask, int B, int Lq, int Lk, int nH, int D, int H, int W, int win, int shift, int dtype, float drop_p,
+                     uint64_t seed, const uint8_t* keep, int64_t keep_cells, void* stream);
+size_t vtx_attn_hdw_bwd_workspace(int B, int Lq, int Lk, int nH, int H, int W, int win, int has_bias);
+int vtx_attn_hdw_bwd(const void* q, const void* k, const void* v, int64_t ldq, int64_t ldkv, const void* o, const void* dout,
+                     const float* lse, const float* bias, const uint8_t* mask, void* dq, void* dk, void* dv, int64_t lddq, int64_t lddkv,
+                     float* dbias, void* workspace, size_t ws_bytes, int B, int Lq, int Lk, int nH, int D, int H, int W, int win, int shift,
+                     int dtype, float drop_p, uint64_t seed, const uint8_t* keep, int64_t keep_cells, void* stream);
 
 /* ---- Positional-encoding generator of Twins-SVT (csrc/twins_misc.hip; reference models/twins.py:25-37):
  * y = x + DepthwiseConv3x3(x) on channels-last features x, y [B, H, W, C] (C % 8 == 0, C <= 1024), w = the

@@ -58,8 +58,9 @@ class MultiHeadedHaloAttention(nn.Module):
         w = self.window_size
         if H % w or W % w:
             raise ValueError(f"feature map {(H, W)} is not a multiple of the window size {w}")
-        if self.dim_head not in (32, 64):
-            raise NotImplementedError("vtx: the halo attention kernels are built for head dim 32 or 64")
+        if not VF.ops.attn_hd_supported(self.dim_head):
+            raise NotImplementedError(f"vtx: halo attention needs a head dim that is a multiple of 8 in 8..128 "
+                                      f"(got {self.n_head} heads: head dim {self.dim_head})")
         T = VF.compute_dtype(input)
         qkv = VF.LinearFn.apply(input.to(T), self.weight.weight, None)
         out = VF.HaloAttentionFn.apply(qkv, self.rel_pos.weight, self.meta(), VF.attn_drop(self.dropout, self.training, keep))

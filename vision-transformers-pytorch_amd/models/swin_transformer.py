@@ -84,6 +84,11 @@ class MultiHeadedLocalAttention(nn.Module):
         return self._region[1], self._region[2]
 
     def meta(self, eps=1e-6):
+        # any head width that is a multiple of 8 up to 128 and any window: 32 up to 160 tokens and 64 up to 64 tokens on the register-resident
+        # kernels (32 at windows up to 7 x 7 on the window fast path), everything else on csrc/attention_hd.hip (vtx_attn_hdw_*)
+        if not VF.ops.attn_hd_supported(self.dim_head):
+            raise NotImplementedError(f"vtx: Swin window attention needs a head dim that is a multiple of 8 in 8..128 "
+                                      f"(got {self.n_head} heads: head dim {self.dim_head})")
         w = self.window_size
         region, fast = self.regions()
         return VF.AttentionMeta(

@@ -122,6 +122,9 @@ class MultiHeadedLocalAttention(nn.Module):
     def meta(self, height, width, device, eps=1e-6):
         """Geometry + integer tables of the window-attention kernels for this feature-map size.  The reference module has no
         position bias and no mask: the kernels get an all-zero bias table (S + 0 = S exactly) and the un-shifted geometry."""
+        if not VF.ops.attn_hd_supported(self.dim_head):
+            raise NotImplementedError(f"vtx: the locally-grouped attention needs a head dim that is a multiple of 8 in 8..128 "
+                                      f"(got {self.n_head} heads: head dim {self.dim_head})")
         key = (height, width, str(device))
         m = self._meta.get(key)
         if m is None:
@@ -143,6 +146,13 @@ class MultiHeadedLocalAttention(nn.Module):
     def check(self):
         pass
 
+    def without_table(self):
+        """True where the kernels that are handed the all-zero bias table refuse (head widths other than 32 / 64, 32 beyond 160 tokens, 64
+        beyond 64 tokens: ops.attn_hdw_routes asked WITH a bias).  The attention core then gets no bias at all, as in the reference, and
+        the layer runs call by call: on csrc/attention_hd.hip (vtx_attn_hdw_*) -- except dim_head 64 with 65..224 tokens, which the
+        generic vtx_attention_* kernels take once there is no bias (AttentionCoreFn asks the predicate again, without one)."""
+        return VF.ops.attn_hdw_routes(self.dim_head, self.window_size ** 2, bias=True)
+
     def drops(self):
         """True when F.dropout(attn, self.dropout, self.training) of the reference (twins.py:147) is active."""
         return self.training and self.dropout > 0
@@ -152,7 +162,8 @@ class MultiHeadedLocalAttention(nn.Module):
         T = VF.compute_dtype(input)
         meta, zero_bias = self.meta(input.shape[1], input.shape[2], input.device)
         qkv = VF.LinearFn.apply(input.to(T), self.weight.weight, self.weight.bias)
-        out = VF.AttentionCoreFn.apply(qkv, zero_bias, meta, VF.attn_drop(self.dropout, self.training, keep))
+        out = VF.AttentionCoreFn.apply(qkv, None if self.without_table() else zero_bias, meta,
+                                       VF.attn_drop(self.dropout, self.training, keep))
         return VF.LinearFn.apply(out, self.linear.weight, self.linear.bias)
 
 
@@ -177,7 +188,7 @@ class TransformerLayer(nn.Module):
 
     def forward(self, input):
         if (not (self.ff_local.fused_ok() and self.ff_global.fused_ok()) or self.attn_local.drops() or self.attn_global.drops()
-                or self.attn_global.dim_head not in (32, 64)):          # (global head widths of csrc/attention_hd.hip: call by call)
+                or self.attn_global.dim_head not in (32, 64) or self.attn_local.without_table()):   # (csrc/attention_hd.hip: call by call)
             out = input + self.drop_path(self.attn_local(self.norm_attn_local(input)))
             out = out + self.drop_path(self.ff_local(self.norm_ff_local(out)))
             out = out + self.drop_path(self.attn_global(self.norm_attn_global(out)))

@@ -204,6 +204,12 @@ _SIGNATURES = {
     "vtx_attn_hd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_int64, c_int64, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_float, ctypes.c_uint64,
                                 c_void_p, c_int64, c_void_p]),
+    "vtx_attn_hdw_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                 c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, ctypes.c_uint64, c_void_p, c_int64, c_void_p]),
+    "vtx_attn_hdw_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "vtx_attn_hdw_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int,
+                                 c_int, c_int, c_int, c_int, c_int, c_float, ctypes.c_uint64, c_void_p, c_int64, c_void_p]),
     "vtx_dwconv3_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "vtx_dwconv3_wgrad_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "vtx_dwconv3_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -404,7 +404,7 @@ def _layer_kind(x, rel_pos, meta):
         return 0
     if _wattn_ok(rel_pos, meta):
         return _lib.ATTN_WINDOW
-    if _attn_hd(rel_pos, meta):
+    if _attn_hd(rel_pos, meta) or _attn_hdw(rel_pos, meta):
         return 0                             # (head widths of csrc/attention_hd.hip: call by call, no one-call layer)
     if rel_pos is None and meta.swin is None and meta.mask is None and meta.csr is None:
         return _lib.ATTN_GLOBAL
@@ -698,12 +698,22 @@ def _attn_hd(rel_pos, meta):
     return ops.attn_hd_routes(meta.dim_head, meta.L, swin=meta.swin is not None, bias=rel_pos is not None, mask=meta.mask is not None)
 
 
+def _attn_hdw(rel_pos, meta):
+    """Window attention (Swin, Twins local) at a head width / window the 32 | 64 kernels refuse: vtx_attn_hdw_*."""
+    return meta.swin is not None and ops.attn_hdw_routes(meta.dim_head, meta.L, bias=rel_pos is not None, mask=meta.mask is not None)
+
+
 def _attn_forward(qkv, rel_pos, meta, drop=None):
     """-> (o, lse, aux) where aux is what the matching backward needs (the bias tensor of the generic path)."""
     B = qkv.shape[0]
     if _attn_hd(rel_pos, meta):
         o, lse = ops.attn_hd_fwd(qkv, None, B, meta.L, meta.L, meta.n_head, meta.dim_head, drop=drop)
         return o.view(qkv.shape[:-1] + (meta.n_head * meta.dim_head,)), lse, None
+    if _attn_hdw(rel_pos, meta):
+        bias = ops.relpos_bias(rel_pos.detach(), meta.pos, meta.n_head) if rel_pos is not None else None
+        o, lse = ops.attn_hdw_fwd(qkv, None, B, meta.L, meta.L, meta.n_head, meta.dim_head, swin=meta.swin, bias=bias, mask=meta.mask,
+                                  drop=drop)
+        return o.view(qkv.shape[:-1] + (meta.n_head * meta.dim_head,)), lse, bias
     if drop is None and _wattn_ok(rel_pos, meta):
         o, lse = ops.wattn_fwd(qkv, rel_pos.detach(), meta.pos, meta.region, B, meta.L, meta.n_head, meta.swin)
         return o, lse, None
@@ -718,6 +728,10 @@ def _attn_backward(qkv, o, do, lse, aux, meta, rel_pos=None, defer=False, drop=N
     B = qkv.shape[0]
     if _attn_hd(rel_pos, meta):
         return ops.attn_hd_bwd(qkv, None, o, do, lse, B, meta.L, meta.L, meta.n_head, meta.dim_head, drop=drop), None
+    if _attn_hdw(rel_pos, meta):
+        dqkv, dbias = ops.attn_hdw_bwd(qkv, None, o, do, lse, B, meta.L, meta.L, meta.n_head, meta.dim_head, swin=meta.swin, bias=aux,
+                                       mask=meta.mask, drop=drop)
+        return dqkv, (ops.table_bias_bwd(dbias, meta.csr, meta.ntab, meta.n_head) if aux is not None else None)
     if drop is None and _wattn_ok(rel_pos, meta):
         return ops.wattn_bwd(qkv, o, do, lse, rel_pos.detach(), meta.pos, meta.region, B, meta.L, meta.n_head,
                              meta.swin, meta.ntab, defer=defer)
@@ -767,7 +781,11 @@ class HaloAttentionFn(Function):
         q = ops.window_gather(qkv, B, H, W, 0, hd, w, 0)
         kv = ops.window_gather(qkv, B, H, W, hd, 2 * hd, w, a)
         bias = ops.table_bias(rel_pos.detach(), meta.pos, nH)
-        o, lse = ops.xattn_fwd(q.view(B * nW * Lq, hd), kv.view(B * nW * Lk, 2 * hd), B * nW, Lq, Lk, nH, bias, drop=drop)
+        if ops.attn_hdw_routes(meta.dim_head, None, bias=True):          # head widths other than 32 / 64 (HaloNet's 16): attention_hd.hip
+            o, lse = ops.attn_hdw_fwd(q.view(B * nW * Lq, hd), kv.view(B * nW * Lk, 2 * hd), B * nW, Lq, Lk, nH, meta.dim_head, bias=bias,
+                                      drop=drop)
+        else:
+            o, lse = ops.xattn_fwd(q.view(B * nW * Lq, hd), kv.view(B * nW * Lk, 2 * hd), B * nW, Lq, Lk, nH, bias, drop=drop)
         out = torch.empty((B, H, W, hd), dtype=qkv.dtype, device=qkv.device)
         ops.window_scatter(o, out, B, H, W, 0, hd, w, 0)
         ctx.save_for_backward(q, kv, o, lse, bias)
@@ -782,8 +800,12 @@ class HaloAttentionFn(Function):
         B, H, W, hd, nW, Lq, Lk = ctx.geom
         w, a, nH = meta.window, meta.halo, meta.n_head
         do = ops.window_gather(_c(dout), B, H, W, 0, hd, w, 0)
-        dq, dkv, dbias = ops.xattn_bwd(q.view(B * nW * Lq, hd), kv.view(B * nW * Lk, 2 * hd), o, do.view(B * nW * Lq, hd), lse,
-                                       B * nW, Lq, Lk, nH, bias, drop=ctx.drop)
+        if ops.attn_hdw_routes(meta.dim_head, None, bias=True):
+            dq, dkv, dbias = ops.attn_hdw_bwd(q.view(B * nW * Lq, hd), kv.view(B * nW * Lk, 2 * hd), o, do.view(B * nW * Lq, hd), lse,
+                                              B * nW, Lq, Lk, nH, meta.dim_head, bias=bias, drop=ctx.drop)
+        else:
+            dq, dkv, dbias = ops.xattn_bwd(q.view(B * nW * Lq, hd), kv.view(B * nW * Lk, 2 * hd), o, do.view(B * nW * Lq, hd), lse,
+                                           B * nW, Lq, Lk, nH, bias, drop=ctx.drop)
         dqkv = torch.empty((B, H, W, 3 * hd), dtype=q.dtype, device=q.device)
         ops.window_scatter(dq, dqkv, B, H, W, 0, hd, w, 0)
         ops.window_scatter(dkv, dqkv, B, H, W, hd, 2 * hd, w, a)          # sums over the neighbourhoods that hold a token

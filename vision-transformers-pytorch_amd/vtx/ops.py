@@ -929,6 +929,107 @@ def attn_hd_bwd(q, kv, o, dout, lse, B, Lq, Lk, n_head, D, drop=None):
     return dq if kv is None else (dq, dkv)
 
 
+# ------------------------------------------------------------------------------- window / halo attention at any head width and any window
+def attn_hdw_routes(D, L=None, bias=False, mask=False, drop=False):
+    """True where a WINDOW attention call (``L`` = win * win tokens: Swin, the Twins locally-grouped half) or a CROSS attention call with
+    a score bias (``L=None``: the q | kv pair of halo attention) goes to vtx_attn_hdw_*: exactly where vtx_attention_* with swin != 0 and
+    vtx_xattn_* refuse -- head widths other than 32 / 64 at any size; 32 beyond 160 tokens; 64 beyond 224 tokens, and with a bias beyond
+    64 (the register-resident bias gradient ends at 10 key tiles, which head dim 64 leaves at 64 tokens).  The dropout variants have
+    the same limits; the cross entries take any length at 32 / 64.  ``mask`` never moves a limit.  False everywhere else: every shape
+    that runs today keeps its kernel, and widths vtx_attn_hdw_* does not take either keep their refusal.  (Global attention without
+    bias and mask is attn_hd_routes' to decide.)"""
+    if not attn_hd_supported(D):
+        return False
+    if D not in (32, 64):
+        return True
+    if L is None:
+        return False
+    if D == 32:
+        return L > 160
+    return L > 224 or (bool(bias) and L > 64)
+
+
+def _attn_hdw_args(q, kv, B, Lq, Lk, n_head, D, swin, bias, mask):
+    """-> (q, k, v views, ldq, ldkv, problems, (H, W, win, shift), the mask as uint8).  swin = (H, W, win, shift): q is the packed QKV
+    projection of the (B, H, W) map; swin None: plain rows (kv None: packed QKV [B*L, 3 h D]; else the q | kv pair)."""
+    H, W, win, shift = swin if swin is not None else (0, 0, 0, 0)
+    nprob = B
+    if swin is not None:
+        if kv is not None or win <= 0 or H % win or W % win or Lq != win * win or Lk != Lq:
+            raise VtxError(f"vtx: attn_hdw window geometry mismatch ({H} x {W} map, window {win}, {Lq} x {Lk} tokens)")
+        nW = (H // win) * (W // win)
+        nprob = B * nW
+        qv, kk, vv, ldq, ldkv = _attn_hd_views(q, None, nprob, Lq, Lk, n_head, D)
+    else:
+        if mask is not None:
+            raise VtxError("vtx: attn_hdw takes a mask only with a window (it is indexed by the window)")
+        qv, kk, vv, ldq, ldkv = _attn_hd_views(q, kv, B, Lq, Lk, n_head, D)
+    _dev(bias, mask)
+    if bias is not None:
+        _f32(bias, "bias")
+        if bias.numel() != n_head * Lq * Lk or not bias.is_contiguous():
+            raise VtxError(f"vtx: attn_hdw bias must be a contiguous [{n_head}, {Lq}, {Lk}] fp32 tensor")
+    if mask is not None:
+        msk = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+        if msk.dtype != torch.uint8 or not msk.is_contiguous() or msk.numel() != (nprob // B) * Lq * Lk:
+            raise VtxError(f"vtx: attn_hdw mask must be a contiguous [{nprob // B}, {Lq}, {Lk}] bool / uint8 tensor")
+        mask = msk
+    return qv, kk, vv, ldq, ldkv, nprob, (H, W, win, int(bool(shift))), mask
+
+
+def attn_hdw_fwd(q, kv, B, Lq, Lk, n_head, D, swin=None, bias=None, mask=None, drop=None):
+    """o, lse = softmax(q k^T / sqrt(D) + bias, masked cells -inf) v at any head width D % 8 == 0, 8 <= D <= 128 and any window.
+    swin = (H, W, win, shift): q is the packed QKV projection of B images in map order (B, H, W, 3 h D), o comes back in map order
+    [B*H*W, h*D], lse [B*nW*h*L]; swin None: B problems of plain rows, packed (kv None) or the q | kv pair.  bias fp32 [h, Lq, Lk];
+    mask bool / uint8 [nW, Lq, Lk] (window mode only; every query row keeps at least one key); drop = (p, seed, keep [problems*h, Lq, Lk])."""
+    qv, kk, vv, ldq, ldkv, nprob, (H, W, win, shift), mask = _attn_hdw_args(q, kv, B, Lq, Lk, n_head, D, swin, bias, mask)
+    hd = n_head * D
+    o = torch.empty((nprob * Lq, hd), dtype=q.dtype, device=q.device)
+    lse = torch.empty(nprob * n_head * Lq, dtype=torch.float32, device=q.device)
+    tn = "__bf16" if q.dtype == torch.bfloat16 else "float"
+    ev = _attn_bracket(f"hdattn_fwd_kernel<{tn}, {attn_hd_pad(D)}, true>", nprob * n_head, Lq, D, nprob * Lq, hd, q.element_size(), False)
+    if ev is not None:
+        _timer.records[-1] = (_timer.records[-1][0], 4.0 * nprob * n_head * Lq * Lk * D,
+                              q.element_size() * (2.0 * nprob * Lq * hd + 2.0 * nprob * Lk * hd)) + _timer.records[-1][3:]
+    dp, seed, keep, cells = _attn_hd_drop(drop, q.device, nprob * n_head * Lq * Lk)
+    check(_lib.load().vtx_attn_hdw_fwd(_p(qv), _p(kk), _p(vv), ldq, ldkv, _p(o), _p(lse), _p(bias), _p(mask), B, Lq, Lk, n_head, D, H, W, win,
+                                       shift, _dt(q), dp, seed, _p(keep), cells, _stream()), "vtx_attn_hdw_fwd")
+    if ev:
+        ev[1].record()
+    return o, lse
+
+
+def attn_hdw_bwd(q, kv, o, dout, lse, B, Lq, Lk, n_head, D, swin=None, bias=None, mask=None, drop=None):
+    """-> (dqkv, dbias) in the packed layout (kv None; map order with swin) or (dq, dkv, dbias); dbias fp32 [h, Lq, Lk] = the sum of dS
+    over all problems (None without a bias), deterministic; drop: the forward's (p, seed, keep)."""
+    qv, kk, vv, ldq, ldkv, nprob, (H, W, win, shift), mask = _attn_hdw_args(q, kv, B, Lq, Lk, n_head, D, swin, bias, mask)
+    _dev(o, dout, lse)
+    _f32(lse, "lse")
+    hd = n_head * D
+    if o.dtype != q.dtype or dout.dtype != q.dtype or o.numel() != nprob * Lq * hd or dout.numel() != nprob * Lq * hd or \
+            lse.numel() != nprob * n_head * Lq or not o.is_contiguous() or not dout.is_contiguous():
+        raise VtxError("vtx: attn_hdw backward operands do not match the forward's (o, dout [rows, h*D] of q's dtype, lse [problems*h*Lq])")
+    lib = _lib.load()
+    dq = torch.empty_like(q)
+    dkv = torch.empty_like(kv) if kv is not None else None
+    dqv, dkk, dvv, _, _ = _attn_hd_views(dq, dkv, nprob if kv is None else B, Lq, Lk, n_head, D)
+    dbias = torch.empty((n_head, Lq, Lk), dtype=torch.float32, device=q.device) if bias is not None else None
+    wsb = lib.vtx_attn_hdw_bwd_workspace(B, Lq, Lk, n_head, H, W, win, int(bias is not None))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
+    tn = "__bf16" if q.dtype == torch.bfloat16 else "float"
+    ev = _attn_bracket(f"hdattn_bwd_*_kernel<{tn}, {attn_hd_pad(D)}, true>", nprob * n_head, Lq, D, nprob * Lq, hd, q.element_size(), True)
+    if ev is not None:
+        _timer.records[-1] = (_timer.records[-1][0], (14.0 if bias is not None else 10.0) * nprob * n_head * Lq * Lk * D,
+                              q.element_size() * (4.0 * nprob * Lq * hd + 4.0 * nprob * Lk * hd)) + _timer.records[-1][3:]
+    dp, seed, keep, cells = _attn_hd_drop(drop, q.device, nprob * n_head * Lq * Lk)
+    check(lib.vtx_attn_hdw_bwd(_p(qv), _p(kk), _p(vv), ldq, ldkv, _p(o), _p(dout), _p(lse), _p(bias), _p(mask), _p(dqv), _p(dkk), _p(dvv),
+                               ldq, ldkv, _p(dbias), _p(ws), wsb, B, Lq, Lk, n_head, D, H, W, win, shift, _dt(q), dp, seed, _p(keep), cells,
+                               _stream()), "vtx_attn_hdw_bwd")
+    if ev:
+        ev[1].record()
+    return (dq, dbias) if kv is None else (dq, dkv, dbias)
+
+
 def dwconv3_fwd(x, w, adjoint=False):
     """y = x + DepthwiseConv3x3(x) on channels-last x (B, H, W, C), w (C, 1, 3, 3) fp32 -- twins.py:25-37; adjoint: the input
     gradient of the same map (x := dy)."""
