@@ -2,6 +2,7 @@
 
   vtx._lib        ctypes binding of libvtx.so (C ABI in include/vtx.h) -- no fallback
   vtx.ops         tensor-level wrappers, one per C entry point
+  vtx.attention   the attention wrappers (reached as vtx.ops.*), their kernel-family router and their one launch helper
   vtx.functional  autograd.Functions (fused forward/backward kernel sequences)
   vtx.nn          nn.Linear / nn.LayerNorm parameter containers with HIP forwards
   vtx.tables      integer window tables (pos / local_mask), bit-exact vs the reference

@@ -16,7 +16,7 @@ import warnings
 import torch
 from torch.autograd import Function
 
-from . import _lib, ops, options
+from . import _lib, attention, ops, options
 from .ops import ACT_DGELU, ACT_DSILU, ACT_GELU, ACT_SILU, VtxError
 
 
@@ -402,13 +402,12 @@ _ALIGN = 256
 def _layer_kind(x, rel_pos, meta):
     if not (_LAYER_CALL and _DEFER_REDUCE and x.is_cuda):
         return 0
-    if _wattn_ok(rel_pos, meta):
+    route = _route(rel_pos, meta)
+    if route == "window":
         return _lib.ATTN_WINDOW
-    if _attn_hd(rel_pos, meta) or _attn_hdw(rel_pos, meta):
-        return 0                             # (head widths of csrc/attention_hd.hip: call by call, no one-call layer)
-    if rel_pos is None and meta.swin is None and meta.mask is None and meta.csr is None:
+    if route == "generic" and rel_pos is None and meta.swin is None and meta.mask is None and meta.csr is None:
         return _lib.ATTN_GLOBAL
-    return 0
+    return 0                                 # ("hd" / "hdw", csrc/attention_hd.hip, included: call by call, no one-call layer)
 
 
 class _LayerPlan:
@@ -670,11 +669,6 @@ class AttentionMeta:
         self.region, self.fast = region, fast
 
 
-def _wattn_ok(rel_pos, meta):
-    return (rel_pos is not None and meta.swin is not None and meta.fast and
-            ops.wattn_supported(meta.dim_head, meta.swin[2]) and (meta.mask is None or meta.region is not None))
-
-
 def attn_drop(p, training, keep=None):
     """(p, seed, keep) of one attention-dropout call, None when the reference's F.dropout(attn, p, training) is the identity.
     The 64-bit seed of the counter-based mask hash is DRAWN FROM TORCH'S GENERATOR (one CPU `randint` per active call, ~5 us of host
@@ -693,46 +687,46 @@ def attn_drop(p, training, keep=None):
     return (float(p), seed, keep)
 
 
-def _attn_hd(rel_pos, meta):
-    """Global attention (no window, no rel_pos, no mask) at a head width / length the 32 | 64 kernels refuse: vtx_attn_hd_*."""
-    return ops.attn_hd_routes(meta.dim_head, meta.L, swin=meta.swin is not None, bias=rel_pos is not None, mask=meta.mask is not None)
+def _route(rel_pos, meta, drop=None):
+    """Kernel family of an attention call on the packed QKV projection: "hd" | "hdw" | "window" | "generic" (attention.route_packed)."""
+    return attention.route_packed(meta.dim_head, meta.L, meta.swin, rel_pos is not None, meta.mask is not None, meta.region is not None,
+                                  meta.fast, drop)
 
 
 def _attn_hdw(rel_pos, meta):
     """Window attention (Swin, Twins local) at a head width / window the 32 | 64 kernels refuse: vtx_attn_hdw_*."""
-    return meta.swin is not None and ops.attn_hdw_routes(meta.dim_head, meta.L, bias=rel_pos is not None, mask=meta.mask is not None)
+    return _route(rel_pos, meta) == "hdw"
 
 
-def _attn_forward(qkv, rel_pos, meta, drop=None):
-    """-> (o, lse, aux) where aux is what the matching backward needs (the bias tensor of the generic path)."""
+def _attn_forward(qkv, rel_pos, meta, route, drop=None):
+    """-> (o, lse, aux) on ``route``, where aux is what the matching backward needs (the bias tensor of the generic and hdw paths)."""
     B = qkv.shape[0]
-    if _attn_hd(rel_pos, meta):
+    if route == "hd":
         o, lse = ops.attn_hd_fwd(qkv, None, B, meta.L, meta.L, meta.n_head, meta.dim_head, drop=drop)
         return o.view(qkv.shape[:-1] + (meta.n_head * meta.dim_head,)), lse, None
-    if _attn_hdw(rel_pos, meta):
-        bias = ops.relpos_bias(rel_pos.detach(), meta.pos, meta.n_head) if rel_pos is not None else None
-        o, lse = ops.attn_hdw_fwd(qkv, None, B, meta.L, meta.L, meta.n_head, meta.dim_head, swin=meta.swin, bias=bias, mask=meta.mask,
-                                  drop=drop)
-        return o.view(qkv.shape[:-1] + (meta.n_head * meta.dim_head,)), lse, bias
-    if drop is None and _wattn_ok(rel_pos, meta):
+    if route == "window":
         o, lse = ops.wattn_fwd(qkv, rel_pos.detach(), meta.pos, meta.region, B, meta.L, meta.n_head, meta.swin)
         return o, lse, None
     bias = ops.relpos_bias(rel_pos.detach(), meta.pos, meta.n_head) if rel_pos is not None else None
+    if route == "hdw":
+        o, lse = ops.attn_hdw_fwd(qkv, None, B, meta.L, meta.L, meta.n_head, meta.dim_head, swin=meta.swin, bias=bias, mask=meta.mask,
+                                  drop=drop)
+        return o.view(qkv.shape[:-1] + (meta.n_head * meta.dim_head,)), lse, bias
     o, lse = ops.attention_fwd(qkv, B, meta.L, meta.n_head, meta.dim_head, swin=meta.swin, bias=bias, mask=meta.mask, drop=drop)
     return o, lse, bias
 
 
-def _attn_backward(qkv, o, do, lse, aux, meta, rel_pos=None, defer=False, drop=None):
-    """-> dqkv, drel_pos (an ops.Partials with ``defer`` on the window-attention fast path: reduced later in one launch
-    with the layer's LayerNorm partials)."""
+def _attn_backward(qkv, o, do, lse, aux, meta, route, rel_pos=None, defer=False, drop=None):
+    """-> dqkv, drel_pos on ``route`` = the forward's (an ops.Partials with ``defer`` on the window-attention fast path: reduced later
+    in one launch with the layer's LayerNorm partials)."""
     B = qkv.shape[0]
-    if _attn_hd(rel_pos, meta):
+    if route == "hd":
         return ops.attn_hd_bwd(qkv, None, o, do, lse, B, meta.L, meta.L, meta.n_head, meta.dim_head, drop=drop), None
-    if _attn_hdw(rel_pos, meta):
+    if route == "hdw":
         dqkv, dbias = ops.attn_hdw_bwd(qkv, None, o, do, lse, B, meta.L, meta.L, meta.n_head, meta.dim_head, swin=meta.swin, bias=aux,
                                        mask=meta.mask, drop=drop)
         return dqkv, (ops.table_bias_bwd(dbias, meta.csr, meta.ntab, meta.n_head) if aux is not None else None)
-    if drop is None and _wattn_ok(rel_pos, meta):
+    if route == "window":
         return ops.wattn_bwd(qkv, o, do, lse, rel_pos.detach(), meta.pos, meta.region, B, meta.L, meta.n_head,
                              meta.swin, meta.ntab, defer=defer)
     return ops.attention_bwd(qkv, o, do, lse, B, meta.L, meta.n_head, meta.dim_head, swin=meta.swin, bias=aux,
@@ -745,7 +739,8 @@ class AttentionCoreFn(Function):
     @staticmethod
     def forward(ctx, qkv, rel_pos, meta, drop=None):
         qkv = _c(qkv)
-        o, lse, aux = _attn_forward(qkv, rel_pos, meta, drop)
+        ctx.route = _route(rel_pos, meta, drop)
+        o, lse, aux = _attn_forward(qkv, rel_pos, meta, ctx.route, drop)
         ctx.save_for_backward(qkv, o, lse, aux, rel_pos)
         ctx.meta, ctx.drop = meta, drop
         return o
@@ -754,7 +749,7 @@ class AttentionCoreFn(Function):
     def backward(ctx, do):
         side_fence(do.device)
         qkv, o, lse, aux, rel_pos = ctx.saved_tensors
-        dqkv, drel = _attn_backward(qkv, o, _c(do), lse, aux, ctx.meta, rel_pos, drop=ctx.drop)
+        dqkv, drel = _attn_backward(qkv, o, _c(do), lse, aux, ctx.meta, ctx.route, rel_pos, drop=ctx.drop)
         return dqkv, drel, None, None
 
 
@@ -781,7 +776,8 @@ class HaloAttentionFn(Function):
         q = ops.window_gather(qkv, B, H, W, 0, hd, w, 0)
         kv = ops.window_gather(qkv, B, H, W, hd, 2 * hd, w, a)
         bias = ops.table_bias(rel_pos.detach(), meta.pos, nH)
-        if ops.attn_hdw_routes(meta.dim_head, None, bias=True):          # head widths other than 32 / 64 (HaloNet's 16): attention_hd.hip
+        ctx.route = attention.route_pair(meta.dim_head, True)
+        if ctx.route == "hdw":                                           # head widths other than 32 / 64 (HaloNet's 16): attention_hd.hip
             o, lse = ops.attn_hdw_fwd(q.view(B * nW * Lq, hd), kv.view(B * nW * Lk, 2 * hd), B * nW, Lq, Lk, nH, meta.dim_head, bias=bias,
                                       drop=drop)
         else:
@@ -800,7 +796,7 @@ class HaloAttentionFn(Function):
         B, H, W, hd, nW, Lq, Lk = ctx.geom
         w, a, nH = meta.window, meta.halo, meta.n_head
         do = ops.window_gather(_c(dout), B, H, W, 0, hd, w, 0)
-        if ops.attn_hdw_routes(meta.dim_head, None, bias=True):
+        if ctx.route == "hdw":
             dq, dkv, dbias = ops.attn_hdw_bwd(q.view(B * nW * Lq, hd), kv.view(B * nW * Lk, 2 * hd), o, do.view(B * nW * Lq, hd), lse,
                                               B * nW, Lq, Lk, nH, meta.dim_head, bias=bias, drop=ctx.drop)
         else:
@@ -846,7 +842,8 @@ class TransformerLayerFn(Function):
         ln1, mean1, rstd1 = ops.layernorm_fwd(x, ln1_w.detach(), ln1_b.detach(), meta.eps)
         wq, wo, w1, w2 = ctx.wp = (wcast(qkv_w, T), wcast(proj_w, T), wcast(fc1_w, T), wcast(fc2_w, T))
         qkv = ops.gemm(ln1, wq[0], 0, bias=qkv_b.detach())
-        o, lse, bias = _attn_forward(qkv, rel_pos, meta)
+        ctx.route = _route(rel_pos, meta)
+        o, lse, bias = _attn_forward(qkv, rel_pos, meta, ctx.route)
         x1 = ops.gemm(o, wo[0], 0, bias=proj_b.detach(), resid=x, rowscale=s1, rows_per_scale=rps)
         ln2, mean2, rstd2 = ops.layernorm_fwd(x1, ln2_w.detach(), ln2_b.detach(), meta.eps)
         h, z = _act_gemm(ctx, ln2, w1[0], fc1_b.detach(), ACT_SILU)
@@ -992,7 +989,7 @@ class TransformerLayerFn(Function):
             dx1, dg2, dbe2 = ops.layernorm_bwd(dln2, x1, mean2, rstd2, ln2_w.detach(), dres=dy)
         # ---- attention branch
         do = dgrad(dx1, wo, T, rowscale=s1, rows_per_scale=rps)
-        dqkv, drel = _attn_backward(qkv, o, do, lse, bias, m, rel_pos, defer=_DEFER_REDUCE)
+        dqkv, drel = _attn_backward(qkv, o, do, lse, bias, m, ctx.route, rel_pos, defer=_DEFER_REDUCE)
         dln1 = dgrad(dqkv, wq, T)
         if _DEFER_REDUCE:
             dx, part1 = ops.layernorm_bwd(dln1, x, mean1, rstd1, ln1_w.detach(), dres=dx1, defer=True)
@@ -1196,8 +1193,8 @@ class SrAttentionFn(Function):
     def forward(ctx, q, kv, B, Lq, Lk, n_head, drop=None):
         q, kv = _c(q), _c(kv)
         D = q.shape[-1] // n_head
-        ctx.hd = D if ops.attn_hd_routes(D) else 0          # widths other than 32 / 64: csrc/attention_hd.hip, at any Lk
-        if ctx.hd:
+        ctx.route = attention.route_pair(D, False)
+        if ctx.route == "hd":                               # widths other than 32 / 64: csrc/attention_hd.hip, at any Lk
             o, lse = ops.attn_hd_fwd(q, kv, B, Lq, Lk, n_head, D, drop=drop)
             o = o.view(q.shape)
         else:
@@ -1210,8 +1207,8 @@ class SrAttentionFn(Function):
     def backward(ctx, do):
         side_fence(do.device)
         q, kv, o, lse = ctx.saved_tensors
-        if ctx.hd:
-            dq, dkv = ops.attn_hd_bwd(q, kv, o, _c(do), lse, *ctx.geom, ctx.hd, drop=ctx.drop)
+        if ctx.route == "hd":
+            dq, dkv = ops.attn_hd_bwd(q, kv, o, _c(do), lse, *ctx.geom, q.shape[-1] // ctx.geom[3], drop=ctx.drop)
         else:
             dq, dkv = ops.srattn_bwd(q, kv, o, _c(do), lse, *ctx.geom, drop=ctx.drop)
         return dq, dkv, None, None, None, None, None

@@ -225,19 +225,6 @@ def timing():
     return _timer is not None
 
 
-def _attn_bracket(name, nprob, L, D, rows, hd, es, bwd):
-    """HIP-event bracket of an attention launch: algorithmic FLOPs 2*2*L^2*D per problem forward (QK^T, PV), 5 products
-    backward (S, dP, dV, dQ, dK); algorithmic bytes q,k,v read + o written (forward) / q,k,v,o,do read + dq,dk,dv
-    written (backward) -- scores never touch HBM."""
-    if _timer is None:
-        return None
-    flops = (10.0 if bwd else 4.0) * nprob * L * L * D
-    nbytes = (8.0 if bwd else 4.0) * rows * hd * es
-    ev = _timer.bracket(name, flops, nbytes)
-    ev[0].record()
-    return ev
-
-
 def set_kernel_timer(timer):
     """Install / remove the per-launch timer.  The launches of the one-call layers (vtx_layer_fwd / _bwd) are timed inside
     libvtx (vtx_timer_start / _stop: HIP events on the launch stream around every launch of a layer call); removing the
@@ -282,10 +269,8 @@ def _describe_timer_rec(r):
     if r.tag in (4, 7):                                                 # global attention: n heads of D, k tokens per image
         bwd = r.tag == 7
         nprob = rows // k * n
-        nkt = 4 if k <= 64 else (8 if k <= 128 else 14)
-        fast = bf and D == 64 and k <= 224 and options.get("SATTN")
-        name = (f"sattn_{'bwd' if bwd else 'fwd'}_kernel<{nkt}, {_sattn_cfg(k)}>" if fast else
-                ("lattn_*_kernel" if k > 224 else f"attn_{'bwd' if bwd else 'fwd'}_kernel"))
+        # (beyond SHORT_MAX tokens these records keep one name for both directions)
+        name = "lattn_*_kernel" if k > SHORT_MAX else generic_label(dt, D, k, False, False, False, False, bwd)
         return name, (10.0 if bwd else 4.0) * nprob * k * k * D, (8.0 if bwd else 4.0) * rows * n * D * es, r.ms
     if r.tag == 8:                                                      # the layer's grouped weight gradient: n = C, k = ff
         C, ff = n, k
@@ -336,24 +321,6 @@ def _describe_timer_rec(r):
     if r.tag == 18:                                                     # LayerNorm forward on the row operands of a streaming GEMM: rows x n over k = C
         return (f"gemm_skinny_kernel<{k // 32}, 0, false, 4, true>", 2.0 * rows * n * k, float(es * (rows * (2 * k + n) + n * k) + 8.0 * rows), r.ms)
     return f"vtx_layer launch (tag {r.tag})", 0.0, 0.0, r.ms
-
-
-def wattn_fwd_kernel_name(dtype, masked, nbn):
-    """Mirrors wattn_fwd_launch (attention_win.hip): bf16 with >= 4 096 (image, window) problems per head takes the four-wave kernel
-    (option WATTN_FWD4: 1 | 2 always | 0 never)."""
-    m = "true" if masked else "false"
-    f4 = options.get("WATTN_FWD4")
-    if dtype == torch.bfloat16 and (f4 >= 2 or (f4 == 1 and nbn >= 4096)):
-        return f"wattn_fwd4_kernel<{m}>"
-    return f"wattn_fwd_kernel<{'__bf16' if dtype == torch.bfloat16 else 'float'}, {m}>"
-
-
-def wattn_bwd_kernel_name(dtype, masked, inverse_map=True):
-    """Mirrors wattn_bwd_launch (attention_win.hip): bf16 with the inverse pos map takes the four-wave kernel."""
-    m = "true" if masked else "false"
-    if dtype == torch.bfloat16 and inverse_map and options.get("WATTN_BWD4"):
-        return f"wattn_bwd4_kernel<{m}>"
-    return f"wattn_bwd_kernel<{'__bf16' if dtype == torch.bfloat16 else 'float'}, {m}>"
 
 
 def skinny_ok(N, K, M, vec=False):
@@ -646,388 +613,6 @@ def wgrad_group(jobs, rows_per_scale=1, scale_const=0.0, outs=None, colparts=Non
         return None
     res = list(zip(dWs, dbs))
     return (res, couts) if colparts is not None else res
-
-
-# ------------------------------------------------------------------------------- PVT / Twins: spatial-reduction attention
-def _sr_head_dim(q, kv, B, Lq, Lk, n_head):
-    """Head dim of the operands (64: PVT, 32: Twins-SVT); the kernels exist for these two."""
-    if q.dtype != kv.dtype:
-        raise VtxError("vtx: srattn operand dtypes differ")
-    hd = q.numel() // max(B * Lq, 1)
-    D = hd // max(n_head, 1)
-    if D not in (32, 64) or D * n_head != hd or q.numel() != B * Lq * hd or kv.numel() != B * Lk * 2 * hd:
-        raise VtxError(f"vtx: srattn shape mismatch (q {tuple(q.shape)}, kv {tuple(kv.shape)}, {n_head} heads: head dim must be 32 or 64)")
-    return D, hd
-
-
-def _drop_args(drop, dev, cells=None):
-    """(p, seed, keep) of an attention-dropout call -> (float p, int seed, keep pointer); keep: uint8 [problems][Lq][Lk] or None.
-    ``cells`` = problems * Lq * Lk of THIS call: a keep mask of any other size (a transposed or per-image layout) would be read out of
-    bounds by the kernels' drop_factor -- refused here, forward and backward alike."""
-    p, seed, keep = drop
-    if not 0.0 < float(p) < 1.0:
-        raise VtxError(f"vtx: attention dropout probability {p} outside (0, 1)")
-    if keep is not None:
-        _dev(keep)
-        if keep.dtype != torch.uint8 or not keep.is_contiguous():
-            raise VtxError("vtx: attention keep mask must be a contiguous uint8 tensor")
-        if cells is not None and keep.numel() != cells:
-            raise VtxError(f"vtx: attention keep mask has {keep.numel()} cells, this call needs [problems, Lq, Lk] = {cells}")
-    return float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, keep
-
-
-def attn_keep_mask(nprob, Lq, Lk, p, seed, device):
-    """uint8 [nprob, Lq, Lk]: the keep decisions the dropout kernels regenerate from (p, seed) -- tests / external checkers."""
-    out = torch.empty((nprob, Lq, Lk), dtype=torch.uint8, device=device)
-    check(_lib.load().vtx_attn_keep_mask(_p(out), nprob, Lq, Lk, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, _stream()),
-          "vtx_attn_keep_mask")
-    return out
-
-
-def srattn_fwd(q, kv, B, Lq, Lk, n_head, drop=None):
-    """o [B*Lq, h*D], lse from q [B*Lq, h*D] and kv [B*Lk, 2*h*D] (k | v) -- reference models/pvt.py:38-66, twins.py:56-93.
-    drop = (p, seed, keep): dropout of the attention probabilities (pvt.py:60)."""
-    _dev(q, kv)
-    D, hd = _sr_head_dim(q, kv, B, Lq, Lk, n_head)
-    o = torch.empty_like(q)
-    lse = torch.empty(B * n_head * Lq, dtype=torch.float32, device=q.device)
-    tn = "__bf16" if q.dtype == torch.bfloat16 else "float"
-    ev = _attn_bracket(f"srattn_fwd_kernel<{tn}, {D}>", B * n_head, Lq, D, B * Lq, hd, q.element_size(), False)
-    if ev is not None:                              # Lq x Lk products, not Lq x Lq
-        _timer.records[-1] = (_timer.records[-1][0], 4.0 * B * n_head * Lq * Lk * D,
-                              q.element_size() * (2.0 * B * Lq * hd + 2.0 * B * Lk * hd)) + _timer.records[-1][3:]
-    if drop is not None:
-        dp, seed, keep = _drop_args(drop, q.device, B * n_head * Lq * Lk)
-        check(_lib.load().vtx_srattn_fwd_drop(_p(q), _p(kv), _p(o), _p(lse), B, Lq, Lk, n_head, D, _dt(q), dp, seed, _p(keep),
-                                              _stream()), "vtx_srattn_fwd_drop")
-    else:
-        check(_lib.load().vtx_srattn_fwd(_p(q), _p(kv), _p(o), _p(lse), B, Lq, Lk, n_head, D, _dt(q), _stream()),
-              "vtx_srattn_fwd")
-    if ev:
-        ev[1].record()
-    return o, lse
-
-
-def srattn_scores(q, kv, B, Lq, Lk, n_head):
-    """Pre-softmax scores q k^T / sqrt(D) as (B, n_head, Lq, Lk) -- what pvt.MultiHeadedAttention.forward returns second."""
-    _dev(q, kv)
-    D, _ = _sr_head_dim(q, kv, B, Lq, Lk, n_head)
-    score = torch.empty((B, n_head, Lq, Lk), dtype=q.dtype, device=q.device)
-    check(_lib.load().vtx_srattn_scores(_p(q), _p(kv), _p(score), B, Lq, Lk, n_head, D, _dt(q), _stream()), "vtx_srattn_scores")
-    return score
-
-
-def srattn_bwd(q, kv, o, dout, lse, B, Lq, Lk, n_head, drop=None):
-    """dq, dkv (deterministic); drop: the forward's (p, seed, keep)."""
-    _dev(q, kv, o, dout, lse)
-    lib = _lib.load()
-    D, hd = _sr_head_dim(q, kv, B, Lq, Lk, n_head)
-    dq = torch.empty_like(q)
-    dkv = torch.empty_like(kv)
-    wsb = lib.vtx_srattn_bwd_workspace(B, Lq, Lk, n_head, D)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
-    tn = "__bf16" if q.dtype == torch.bfloat16 else "float"
-    ev = _attn_bracket(f"srattn_bwd_kernel<{tn}, {D}>", B * n_head, Lq, D, B * Lq, hd, q.element_size(), True)
-    if ev is not None:
-        _timer.records[-1] = (_timer.records[-1][0], 10.0 * B * n_head * Lq * Lk * D,
-                              q.element_size() * (4.0 * B * Lq * hd + 4.0 * B * Lk * hd)) + _timer.records[-1][3:]
-    if drop is not None:
-        dp, seed, keep = _drop_args(drop, q.device, B * n_head * Lq * Lk)
-        check(lib.vtx_srattn_bwd_drop(_p(q), _p(kv), _p(o), _p(dout), _p(lse), _p(dq), _p(dkv), _p(ws), wsb, B, Lq, Lk, n_head, D,
-                                      _dt(q), dp, seed, _p(keep), _stream()), "vtx_srattn_bwd_drop")
-    else:
-        check(lib.vtx_srattn_bwd(_p(q), _p(kv), _p(o), _p(dout), _p(lse), _p(dq), _p(dkv), _p(ws), wsb, B, Lq, Lk, n_head, D,
-                                 _dt(q), _stream()), "vtx_srattn_bwd")
-    if ev:
-        ev[1].record()
-    return dq, dkv
-
-
-# ------------------------------------------------------------------------------- halo attention (models/halo_transformer.py:22-115)
-def window_gather(x, B, H, W, c0, nc, win, halo):
-    """[B * nW, (win + 2 halo)^2, nc] neighbourhoods (zero rows outside the map) of channels [c0, c0 + nc) of the map x (B, H, W, ld)."""
-    _dev(x)
-    ld = x.shape[-1]
-    if x.numel() != B * H * W * ld or not x.is_contiguous():
-        raise VtxError("vtx: window_gather expects a contiguous (B, H, W, C) map")
-    nW, side = (H // win) * (W // win), win + 2 * halo
-    out = torch.empty((B * nW, side * side, nc), dtype=x.dtype, device=x.device)
-    check(_lib.load().vtx_window_gather(_p(x), _p(out), B, H, W, ld, c0, nc, win, halo, _dt(x), _stream()), "vtx_window_gather")
-    return out
-
-
-def window_scatter(src, out, B, H, W, c0, nc, win, halo):
-    """The adjoint of window_gather into channels [c0, c0 + nc) of the map ``out`` (B, H, W, ld): sums over the neighbourhoods."""
-    _dev(src, out)
-    ld = out.shape[-1]
-    nW, side = (H // win) * (W // win), win + 2 * halo
-    if out.numel() != B * H * W * ld or not out.is_contiguous():
-        raise VtxError("vtx: window_scatter expects a contiguous (B, H, W, C) destination map")
-    if src.dtype != out.dtype or not src.is_contiguous() or src.numel() != B * nW * side * side * nc:
-        raise VtxError(f"vtx: window_scatter source must be a contiguous [{B * nW}, {side * side}, {nc}] tensor of the map's dtype")
-    if c0 < 0 or nc <= 0 or c0 + nc > ld:
-        raise VtxError(f"vtx: window_scatter channels [{c0}, {c0 + nc}) outside the map's {ld}")
-    check(_lib.load().vtx_window_scatter(_p(src), _p(out), B, H, W, ld, c0, nc, win, halo, _dt(out), _stream()), "vtx_window_scatter")
-    return out
-
-
-def table_bias(table, pos, n_head):
-    """bias [n_head, *pos.shape] = table[pos][..., h] for an int64 index tensor of any shape (halo_transformer.py:95-98)."""
-    _dev(table, pos)
-    _f32(table, "rel_pos")
-    if pos.dtype != torch.int64:
-        raise VtxError("vtx: pos must be int64 (the reference's buffer dtype)")
-    bias = torch.empty((n_head,) + tuple(pos.shape), dtype=torch.float32, device=table.device)
-    check(_lib.load().vtx_table_bias(_p(table), _p(pos), _p(bias), pos.numel(), n_head, _stream()), "vtx_table_bias")
-    return bias
-
-
-def table_bias_bwd(full, csr, ntab, n_head):
-    """dtable [ntab, n_head] from the full gradient [n_head, cells] through the CSR (order, offsets) of pos."""
-    order, offsets = csr
-    _dev(full, order, offsets)
-    out = torch.empty((ntab, n_head), dtype=torch.float32, device=full.device)
-    check(_lib.load().vtx_table_bias_bwd(_p(full), _p(order), _p(offsets), _p(out), full.numel() // n_head, n_head, ntab, _stream()),
-          "vtx_table_bias_bwd")
-    return out
-
-
-def xattn_fwd(q, kv, B, Lq, Lk, n_head, bias=None, drop=None):
-    """o, lse = softmax(q k^T / sqrt(D) + bias) v; q [B * Lq, h D], kv [B * Lk, 2 h D], bias [h, Lq, Lk] fp32 or None; drop = (p, seed, keep)."""
-    _dev(q, kv, bias)
-    D, hd = _sr_head_dim(q, kv, B, Lq, Lk, n_head)
-    o = torch.empty_like(q)
-    lse = torch.empty(B * n_head * Lq, dtype=torch.float32, device=q.device)
-    ev = _attn_bracket("lattn_fwd_kernel (cross)", B * n_head, Lq, D, B * Lq, hd, q.element_size(), False)
-    if drop is not None:
-        dp, seed, keep = _drop_args(drop, q.device, B * n_head * Lq * Lk)
-        check(_lib.load().vtx_xattn_fwd_drop(_p(q), _p(kv), _p(o), _p(lse), _p(bias), B, Lq, Lk, n_head, D, _dt(q), dp, seed, _p(keep),
-                                             _stream()), "vtx_xattn_fwd_drop")
-    else:
-        check(_lib.load().vtx_xattn_fwd(_p(q), _p(kv), _p(o), _p(lse), _p(bias), B, Lq, Lk, n_head, D, _dt(q), _stream()), "vtx_xattn_fwd")
-    if ev:
-        ev[1].record()
-    return o, lse
-
-
-def xattn_bwd(q, kv, o, dout, lse, B, Lq, Lk, n_head, bias=None, drop=None):
-    """dq, dkv, dbias (None without a bias): deterministic; drop: the forward's (p, seed, keep)."""
-    _dev(q, kv, o, dout, lse, bias)
-    lib = _lib.load()
-    D, hd = _sr_head_dim(q, kv, B, Lq, Lk, n_head)
-    dq, dkv = torch.empty_like(q), torch.empty_like(kv)
-    dbias = torch.empty_like(bias) if bias is not None else None
-    wsb = lib.vtx_xattn_bwd_workspace(B, Lq, n_head)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
-    ev = _attn_bracket("lattn_bwd_*_kernel (cross)", B * n_head, Lq, D, B * Lq, hd, q.element_size(), True)
-    if drop is not None:
-        dp, seed, keep = _drop_args(drop, q.device, B * n_head * Lq * Lk)
-        check(lib.vtx_xattn_bwd_drop(_p(q), _p(kv), _p(o), _p(dout), _p(lse), _p(bias), _p(dq), _p(dkv), _p(dbias), _p(ws), wsb, B, Lq, Lk,
-                                     n_head, D, _dt(q), dp, seed, _p(keep), _stream()), "vtx_xattn_bwd_drop")
-    else:
-        check(lib.vtx_xattn_bwd(_p(q), _p(kv), _p(o), _p(dout), _p(lse), _p(bias), _p(dq), _p(dkv), _p(dbias), _p(ws), wsb, B, Lq, Lk,
-                                n_head, D, _dt(q), _stream()), "vtx_xattn_bwd")
-    if ev:
-        ev[1].record()
-    return dq, dkv, dbias
-
-
-# ------------------------------------------------------------------------------- global attention at any head width (csrc/attention_hd.hip)
-def attn_hd_supported(D):
-    """Head widths of vtx_attn_hd_*: the multiples of 8 in 8..128."""
-    return isinstance(D, int) and 8 <= D <= 128 and D % 8 == 0
-
-
-def attn_hd_pad(D):
-    """Padded width the kernels are instantiated on (pad columns are zero operands that are never loaded)."""
-    return 32 if D <= 32 else (64 if D <= 64 else (96 if D <= 96 else 128))
-
-
-def attn_hd_routes(D, L=None, swin=False, bias=False, mask=False):
-    """True where a GLOBAL attention call (no window, no rel_pos / bias, no mask) goes to vtx_attn_hd_*: exactly where the entries
-    that served it so far refuse -- head widths other than 32 / 64, and 32 between 161 and 224 tokens on the packed-QKV entry
-    (ATTN_DISPATCH ends at 160, the key-block kernels start at 225).  ``L=None``: the q | kv (sub-sampled) entry, whose 32 / 64 kernels
-    take any length.  Everything else keeps the kernel it has (or its refusal: widths vtx_attn_hd_* does not take either)."""
-    if swin or bias or mask or not attn_hd_supported(D):
-        return False
-    if D not in (32, 64):
-        return True
-    return D == 32 and L is not None and 160 < L <= 224
-
-
-def _attn_hd_views(q, kv, B, Lq, Lk, n_head, D):
-    """(q, k, v) 2-D column views + (ldq, ldkv) of the packed QKV projection (kv None) or the q | kv pair."""
-    if not attn_hd_supported(D):
-        raise VtxError(f"vtx: head dim {D} -- global attention takes the multiples of 8 in 8..128")
-    hd = n_head * D
-    if kv is None:
-        _dev(q)
-        if Lq != Lk or q.numel() != B * Lq * 3 * hd:
-            raise VtxError(f"vtx: attn_hd shape mismatch (qkv {tuple(q.shape)}, {n_head} heads of {D}, {B} x {Lq} tokens)")
-        t = q.view(B * Lq, 3 * hd)
-        return t[:, :hd], t[:, hd:2 * hd], t[:, 2 * hd:], 3 * hd, 3 * hd
-    _dev(q, kv)
-    if q.dtype != kv.dtype or q.numel() != B * Lq * hd or kv.numel() != B * Lk * 2 * hd:
-        raise VtxError(f"vtx: attn_hd shape mismatch (q {tuple(q.shape)}, kv {tuple(kv.shape)}, {n_head} heads of {D})")
-    t = kv.view(B * Lk, 2 * hd)
-    return q.view(B * Lq, hd), t[:, :hd], t[:, hd:], hd, 2 * hd
-
-
-def _attn_hd_drop(drop, dev, cells):
-    if drop is None:
-        return 0.0, 0, None, 0
-    dp, seed, keep = _drop_args(drop, dev, cells)
-    return dp, seed, keep, (cells if keep is not None else 0)
-
-
-def attn_hd_fwd(q, kv, B, Lq, Lk, n_head, D, drop=None):
-    """o [B*Lq, h*D], lse [B*h*Lq] = softmax(q k^T / sqrt(D)) v at any head width D % 8 == 0, 8 <= D <= 128 (no bias, no mask).
-    kv None: q is the packed QKV projection [B*L, 3*h*D] (Lq == Lk); else q [B*Lq, h*D] and kv [B*Lk, 2*h*D] (k | v).
-    drop = (p, seed, keep): dropout of the probabilities; keep uint8 [B*h, Lq, Lk] replaces the hash."""
-    qv, kk, vv, ldq, ldkv = _attn_hd_views(q, kv, B, Lq, Lk, n_head, D)
-    hd = n_head * D
-    o = torch.empty((B * Lq, hd), dtype=q.dtype, device=q.device)
-    lse = torch.empty(B * n_head * Lq, dtype=torch.float32, device=q.device)
-    tn = "__bf16" if q.dtype == torch.bfloat16 else "float"
-    ev = _attn_bracket(f"hdattn_fwd_kernel<{tn}, {attn_hd_pad(D)}>", B * n_head, Lq, D, B * Lq, hd, q.element_size(), False)
-    if ev is not None:                              # Lq x Lk products on the unpadded width
-        _timer.records[-1] = (_timer.records[-1][0], 4.0 * B * n_head * Lq * Lk * D,
-                              q.element_size() * (2.0 * B * Lq * hd + 2.0 * B * Lk * hd)) + _timer.records[-1][3:]
-    dp, seed, keep, cells = _attn_hd_drop(drop, q.device, B * n_head * Lq * Lk)
-    check(_lib.load().vtx_attn_hd_fwd(_p(qv), _p(kk), _p(vv), ldq, ldkv, _p(o), _p(lse), B, Lq, Lk, n_head, D, _dt(q), dp, seed,
-                                      _p(keep), cells, _stream()), "vtx_attn_hd_fwd")
-    if ev:
-        ev[1].record()
-    return o, lse
-
-
-def attn_hd_bwd(q, kv, o, dout, lse, B, Lq, Lk, n_head, D, drop=None):
-    """-> dqkv (packed layout, kv None) or (dq, dkv): every element written, deterministic; drop: the forward's (p, seed, keep)."""
-    qv, kk, vv, ldq, ldkv = _attn_hd_views(q, kv, B, Lq, Lk, n_head, D)
-    _dev(o, dout, lse)
-    _f32(lse, "lse")
-    hd = n_head * D
-    if o.dtype != q.dtype or dout.dtype != q.dtype or o.numel() != B * Lq * hd or dout.numel() != B * Lq * hd or \
-            lse.numel() != B * n_head * Lq:
-        raise VtxError("vtx: attn_hd backward operands do not match the forward's (o, dout [B*Lq, h*D] of q's dtype, lse [B*h*Lq])")
-    lib = _lib.load()
-    dq = torch.empty_like(q)
-    dkv = torch.empty_like(kv) if kv is not None else None
-    dqv, dkk, dvv, _, _ = _attn_hd_views(dq, dkv, B, Lq, Lk, n_head, D)
-    wsb = lib.vtx_attn_hd_bwd_workspace(B, Lq, n_head)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
-    tn = "__bf16" if q.dtype == torch.bfloat16 else "float"
-    ev = _attn_bracket(f"hdattn_bwd_*_kernel<{tn}, {attn_hd_pad(D)}>", B * n_head, Lq, D, B * Lq, hd, q.element_size(), True)
-    if ev is not None:
-        _timer.records[-1] = (_timer.records[-1][0], 10.0 * B * n_head * Lq * Lk * D,
-                              q.element_size() * (4.0 * B * Lq * hd + 4.0 * B * Lk * hd)) + _timer.records[-1][3:]
-    dp, seed, keep, cells = _attn_hd_drop(drop, q.device, B * n_head * Lq * Lk)
-    check(lib.vtx_attn_hd_bwd(_p(qv), _p(kk), _p(vv), ldq, ldkv, _p(o), _p(dout), _p(lse), _p(dqv), _p(dkk), _p(dvv), ldq, ldkv,
-                              _p(ws), wsb, B, Lq, Lk, n_head, D, _dt(q), dp, seed, _p(keep), cells, _stream()), "vtx_attn_hd_bwd")
-    if ev:
-        ev[1].record()
-    return dq if kv is None else (dq, dkv)
-
-
-# ------------------------------------------------------------------------------- window / halo attention at any head width and any window
-def attn_hdw_routes(D, L=None, bias=False, mask=False, drop=False):
-    """True where a WINDOW attention call (``L`` = win * win tokens: Swin, the Twins locally-grouped half) or a CROSS attention call with
-    a score bias (``L=None``: the q | kv pair of halo attention) goes to vtx_attn_hdw_*: exactly where vtx_attention_* with swin != 0 and
-    vtx_xattn_* refuse -- head widths other than 32 / 64 at any size; 32 beyond 160 tokens; 64 beyond 224 tokens, and with a bias beyond
-    64 (the register-resident bias gradient ends at 10 key tiles, which head dim 64 leaves at 64 tokens).  The dropout variants have
-    the same limits; the cross entries take any length at 32 / 64.  ``mask`` never moves a limit.  False everywhere else: every shape
-    that runs today keeps its kernel, and widths vtx_attn_hdw_* does not take either keep their refusal.  (Global attention without
-    bias and mask is attn_hd_routes' to decide.)"""
-    if not attn_hd_supported(D):
-        return False
-    if D not in (32, 64):
-        return True
-    if L is None:
-        return False
-    if D == 32:
-        return L > 160
-    return L > 224 or (bool(bias) and L > 64)
-
-
-def _attn_hdw_args(q, kv, B, Lq, Lk, n_head, D, swin, bias, mask):
-    """-> (q, k, v views, ldq, ldkv, problems, (H, W, win, shift), the mask as uint8).  swin = (H, W, win, shift): q is the packed QKV
-    projection of the (B, H, W) map; swin None: plain rows (kv None: packed QKV [B*L, 3 h D]; else the q | kv pair)."""
-    H, W, win, shift = swin if swin is not None else (0, 0, 0, 0)
-    nprob = B
-    if swin is not None:
-        if kv is not None or win <= 0 or H % win or W % win or Lq != win * win or Lk != Lq:
-            raise VtxError(f"vtx: attn_hdw window geometry mismatch ({H} x {W} map, window {win}, {Lq} x {Lk} tokens)")
-        nW = (H // win) * (W // win)
-        nprob = B * nW
-        qv, kk, vv, ldq, ldkv = _attn_hd_views(q, None, nprob, Lq, Lk, n_head, D)
-    else:
-        if mask is not None:
-            raise VtxError("vtx: attn_hdw takes a mask only with a window (it is indexed by the window)")
-        qv, kk, vv, ldq, ldkv = _attn_hd_views(q, kv, B, Lq, Lk, n_head, D)
-    _dev(bias, mask)
-    if bias is not None:
-        _f32(bias, "bias")
-        if bias.numel() != n_head * Lq * Lk or not bias.is_contiguous():
-            raise VtxError(f"vtx: attn_hdw bias must be a contiguous [{n_head}, {Lq}, {Lk}] fp32 tensor")
-    if mask is not None:
-        msk = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
-        if msk.dtype != torch.uint8 or not msk.is_contiguous() or msk.numel() != (nprob // B) * Lq * Lk:
-            raise VtxError(f"vtx: attn_hdw mask must be a contiguous [{nprob // B}, {Lq}, {Lk}] bool / uint8 tensor")
-        mask = msk
-    return qv, kk, vv, ldq, ldkv, nprob, (H, W, win, int(bool(shift))), mask
-
-
-def attn_hdw_fwd(q, kv, B, Lq, Lk, n_head, D, swin=None, bias=None, mask=None, drop=None):
-    """o, lse = softmax(q k^T / sqrt(D) + bias, masked cells -inf) v at any head width D % 8 == 0, 8 <= D <= 128 and any window.
-    swin = (H, W, win, shift): q is the packed QKV projection of B images in map order (B, H, W, 3 h D), o comes back in map order
-    [B*H*W, h*D], lse [B*nW*h*L]; swin None: B problems of plain rows, packed (kv None) or the q | kv pair.  bias fp32 [h, Lq, Lk];
-    mask bool / uint8 [nW, Lq, Lk] (window mode only; every query row keeps at least one key); drop = (p, seed, keep [problems*h, Lq, Lk])."""
-    qv, kk, vv, ldq, ldkv, nprob, (H, W, win, shift), mask = _attn_hdw_args(q, kv, B, Lq, Lk, n_head, D, swin, bias, mask)
-    hd = n_head * D
-    o = torch.empty((nprob * Lq, hd), dtype=q.dtype, device=q.device)
-    lse = torch.empty(nprob * n_head * Lq, dtype=torch.float32, device=q.device)
-    tn = "__bf16" if q.dtype == torch.bfloat16 else "float"
-    ev = _attn_bracket(f"hdattn_fwd_kernel<{tn}, {attn_hd_pad(D)}, true>", nprob * n_head, Lq, D, nprob * Lq, hd, q.element_size(), False)
-    if ev is not None:
-        _timer.records[-1] = (_timer.records[-1][0], 4.0 * nprob * n_head * Lq * Lk * D,
-                              q.element_size() * (2.0 * nprob * Lq * hd + 2.0 * nprob * Lk * hd)) + _timer.records[-1][3:]
-    dp, seed, keep, cells = _attn_hd_drop(drop, q.device, nprob * n_head * Lq * Lk)
-    check(_lib.load().vtx_attn_hdw_fwd(_p(qv), _p(kk), _p(vv), ldq, ldkv, _p(o), _p(lse), _p(bias), _p(mask), B, Lq, Lk, n_head, D, H, W, win,
-                                       shift, _dt(q), dp, seed, _p(keep), cells, _stream()), "vtx_attn_hdw_fwd")
-    if ev:
-        ev[1].record()
-    return o, lse
-
-
-def attn_hdw_bwd(q, kv, o, dout, lse, B, Lq, Lk, n_head, D, swin=None, bias=None, mask=None, drop=None):
-    """-> (dqkv, dbias) in the packed layout (kv None; map order with swin) or (dq, dkv, dbias); dbias fp32 [h, Lq, Lk] = the sum of dS
-    over all problems (None without a bias), deterministic; drop: the forward's (p, seed, keep)."""
-    qv, kk, vv, ldq, ldkv, nprob, (H, W, win, shift), mask = _attn_hdw_args(q, kv, B, Lq, Lk, n_head, D, swin, bias, mask)
-    _dev(o, dout, lse)
-    _f32(lse, "lse")
-    hd = n_head * D
-    if o.dtype != q.dtype or dout.dtype != q.dtype or o.numel() != nprob * Lq * hd or dout.numel() != nprob * Lq * hd or \
-            lse.numel() != nprob * n_head * Lq or not o.is_contiguous() or not dout.is_contiguous():
-        raise VtxError("vtx: attn_hdw backward operands do not match the forward's (o, dout [rows, h*D] of q's dtype, lse [problems*h*Lq])")
-    lib = _lib.load()
-    dq = torch.empty_like(q)
-    dkv = torch.empty_like(kv) if kv is not None else None
-    dqv, dkk, dvv, _, _ = _attn_hd_views(dq, dkv, nprob if kv is None else B, Lq, Lk, n_head, D)
-    dbias = torch.empty((n_head, Lq, Lk), dtype=torch.float32, device=q.device) if bias is not None else None
-    wsb = lib.vtx_attn_hdw_bwd_workspace(B, Lq, Lk, n_head, H, W, win, int(bias is not None))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
-    tn = "__bf16" if q.dtype == torch.bfloat16 else "float"
-    ev = _attn_bracket(f"hdattn_bwd_*_kernel<{tn}, {attn_hd_pad(D)}, true>", nprob * n_head, Lq, D, nprob * Lq, hd, q.element_size(), True)
-    if ev is not None:
-        _timer.records[-1] = (_timer.records[-1][0], (14.0 if bias is not None else 10.0) * nprob * n_head * Lq * Lk * D,
-                              q.element_size() * (4.0 * nprob * Lq * hd + 4.0 * nprob * Lk * hd)) + _timer.records[-1][3:]
-    dp, seed, keep, cells = _attn_hd_drop(drop, q.device, nprob * n_head * Lq * Lk)
-    check(lib.vtx_attn_hdw_bwd(_p(qv), _p(kk), _p(vv), ldq, ldkv, _p(o), _p(dout), _p(lse), _p(bias), _p(mask), _p(dqv), _p(dkk), _p(dvv),
-                               ldq, ldkv, _p(dbias), _p(ws), wsb, B, Lq, Lk, n_head, D, H, W, win, shift, _dt(q), dp, seed, _p(keep), cells,
-                               _stream()), "vtx_attn_hdw_bwd")
-    if ev:
-        ev[1].record()
-    return (dq, dbias) if kv is None else (dq, dkv, dbias)
 
 
 def dwconv3_fwd(x, w, adjoint=False):
@@ -2044,166 +1629,9 @@ def vit_assemble_bwd(dx):
     return dpatches, dcls, dpos
 
 
-# ------------------------------------------------------------------------------- attention cores
-def relpos_bias(rel_pos, pos, n_head):
-    """bias[h][a][b] = rel_pos[pos[a][b]][h]  (swin_transformer.py:135-136)."""
-    _dev(rel_pos, pos)
-    _f32(rel_pos, "rel_pos")
-    if pos.dtype != torch.int64:
-        raise VtxError("vtx: pos must be int64 (the reference's buffer dtype)")
-    L = pos.shape[0]
-    bias = torch.empty((n_head, L, L), dtype=torch.float32, device=rel_pos.device)
-    check(_lib.load().vtx_relpos_bias(_p(rel_pos), _p(pos), _p(bias), L, n_head, _stream()), "vtx_relpos_bias")
-    return bias
-
-
-def pos_csr(pos, ntab):
-    """Host-side CSR of the pos table: (a,b) pairs grouped by table index (for the dense rel_pos gradient)."""
-    flat = pos.reshape(-1).cpu()
-    order = torch.argsort(flat, stable=True).to(torch.int32)
-    counts = torch.bincount(flat, minlength=ntab)
-    offsets = torch.zeros(ntab + 1, dtype=torch.int32)
-    offsets[1:] = torch.cumsum(counts, 0).to(torch.int32)
-    return order, offsets
-
-
-def _sattn_cfg(L=197):
-    """(tiles per wave step, waves) template arguments of the ViT attention kernels for sequences of L tokens (asks attention_seq.hip)."""
-    w = _lib.load().vtx_sattn_waves(int(L))
-    return "2, 4" if w == 4 else f"1, {w}"
-
-
-def attention_fwd(qkv, B, L, n_head, D, swin=None, bias=None, mask=None, drop=None):
-    """o [rows, h*D], lse.  swin = (H, W, win, shift) for window attention, None for global.
-    drop = (p, seed, keep): dropout of the attention probabilities (vit.py:39, swin_transformer.py:144) on the register-resident
-    kernels; keep: uint8 [problems, L, L] replaces the hash (parity tests)."""
-    _dev(qkv, bias, mask)
-    H, W, win, shift = swin if swin is not None else (0, 0, 0, 0)
-    rows = qkv.numel() // (3 * n_head * D)
-    nW = (H // win) * (W // win) if swin is not None else 1
-    if rows != B * nW * L:
-        raise VtxError("vtx: attention rows mismatch")
-    o = torch.empty(qkv.shape[:-1] + (n_head * D,), dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty(B * nW * n_head * L, dtype=torch.float32, device=qkv.device)
-    fast = drop is None and swin is None and bias is None and qkv.dtype == torch.bfloat16 and D == 64 and L <= 224      # mirrors sattn_ok
-    nkt = 4 if L <= 64 else (8 if L <= 128 else 14)
-    long_ = drop is None and swin is None and bias is None and mask is None and L > 224
-    ev = _attn_bracket(f"sattn_fwd_kernel<{nkt}, {_sattn_cfg(L)}>" if fast else ("lattn_fwd_kernel" if long_ else "attn_fwd_kernel"),
-                       B * nW * n_head, L, D, rows, n_head * D, qkv.element_size(), False)
-    if drop is not None:
-        dp, seed, keep = _drop_args(drop, qkv.device, B * nW * n_head * L * L)
-        check(_lib.load().vtx_attention_fwd_drop(_p(qkv), _p(o), _p(lse), _p(bias), _p(mask), B, L, n_head, D,
-                                                 int(swin is not None), H, W, win, int(bool(shift)), _dt(qkv), dp, seed, _p(keep),
-                                                 _stream()), "vtx_attention_fwd_drop")
-    else:
-        check(_lib.load().vtx_attention_fwd(_p(qkv), _p(o), _p(lse), _p(bias), _p(mask), B, L, n_head, D,
-                                            int(swin is not None), H, W, win, int(bool(shift)), _dt(qkv), _stream()),
-              "vtx_attention_fwd")
-    if ev:
-        ev[1].record()
-    return o, lse
-
-
-def attention_bwd(qkv, o, dout, lse, B, L, n_head, D, swin=None, bias=None, mask=None, csr=None, ntab=0, drop=None):
-    """dqkv, drel_pos (None without bias); drop: the forward's (p, seed, keep)."""
-    _dev(qkv, o, dout, lse, bias, mask)
-    lib = _lib.load()
-    H, W, win, shift = swin if swin is not None else (0, 0, 0, 0)
-    dqkv = torch.empty_like(qkv)
-    drel, ws, wsb, order, offsets = None, None, 0, None, None
-    if bias is not None:
-        order, offsets = csr
-        _dev(order, offsets)
-        drel = torch.empty((ntab, n_head), dtype=torch.float32, device=qkv.device)
-    if bias is not None or (swin is None and L > 224):          # bias-gradient slabs / the long kernels' Dq vector
-        wsb = lib.vtx_attention_bwd_workspace(B, L, n_head, int(swin is not None), H, W, max(win, 1))
-        ws = torch.empty(wsb, dtype=torch.uint8, device=qkv.device)
-    rows = qkv.numel() // (3 * n_head * D)
-    fast = drop is None and swin is None and bias is None and qkv.dtype == torch.bfloat16 and D == 64 and L <= 224
-    nkt = 4 if L <= 64 else (8 if L <= 128 else 14)
-    long_ = drop is None and swin is None and bias is None and mask is None and L > 224
-    ev = _attn_bracket(f"sattn_bwd_kernel<{nkt}, {_sattn_cfg(L)}>" if fast else ("lattn_bwd_*_kernel" if long_ else "attn_bwd_kernel"),
-                       rows // L * n_head, L, D, rows, n_head * D, qkv.element_size(), True)
-    if drop is not None:
-        dp, seed, keep = _drop_args(drop, qkv.device, rows * n_head * L)
-        check(lib.vtx_attention_bwd_drop(_p(qkv), _p(o), _p(dout), _p(lse), _p(bias), _p(mask), _p(order), _p(offsets),
-                                         _p(dqkv), _p(drel), ntab, _p(ws), wsb, B, L, n_head, D, int(swin is not None),
-                                         H, W, win, int(bool(shift)), _dt(qkv), dp, seed, _p(keep), _stream()),
-              "vtx_attention_bwd_drop")
-    else:
-        check(lib.vtx_attention_bwd(_p(qkv), _p(o), _p(dout), _p(lse), _p(bias), _p(mask), _p(order), _p(offsets),
-                                    _p(dqkv), _p(drel), ntab, _p(ws), wsb, B, L, n_head, D, int(swin is not None),
-                                    H, W, win, int(bool(shift)), _dt(qkv), _stream()), "vtx_attention_bwd")
-    if ev:
-        ev[1].record()
-    return dqkv, drel
-
-
-# ------------------------------------------------------------------------------- window attention fast path
-def wattn_supported(D, win):
-    return D == 32 and win <= 7
-
-
-def wattn_fwd(qkv, rel_pos, pos, region, B, L, n_head, swin):
-    """Window attention forward: region = None (un-shifted) or the uint8 [nW, 64] ids of tables.mask_regions."""
-    _dev(qkv, rel_pos, pos, region)
-    _f32(rel_pos, "rel_pos")
-    if pos.dtype != torch.int64:
-        raise VtxError("vtx: pos must be int64 (the reference's buffer dtype)")
-    H, W, win, shift = swin
-    o = torch.empty(qkv.shape[:-1] + (n_head * 32,), dtype=qkv.dtype, device=qkv.device)
-    nW = (H // win) * (W // win)
-    lse = torch.empty(B * nW * n_head * L, dtype=torch.float32, device=qkv.device)
-    ev = _attn_bracket(wattn_fwd_kernel_name(qkv.dtype, region is not None, B * nW), B * nW * n_head, L, 32,
-                       B * nW * L, n_head * 32, qkv.element_size(), False)
-    check(_lib.load().vtx_wattn_fwd(_p(qkv), _p(o), _p(lse), _p(rel_pos), _p(pos), _p(region), B, L, n_head, H, W, win,
-                                    int(bool(shift)), _dt(qkv), _stream()), "vtx_wattn_fwd")
-    if ev:
-        ev[1].record()
-    return o, lse
-
-
-_POS_INVERSE = {}
-
-
-def _pos_inverse(pos, ntab):
-    """Device copy of tables.pos_inverse(pos), built once per pos buffer (host argsort + one upload, first backward only).
-    Keyed by the buffer's address; valid while the tensor it was built from is alive (a module buffer, never written)."""
-    key = (pos.data_ptr(), pos.device, tuple(pos.shape), ntab)
-    hit = _POS_INVERSE.get(key)
-    if hit is None or hit[0]() is None:
-        import weakref
-        from . import tables
-        for k in [k for k, v in _POS_INVERSE.items() if v[0]() is None]:      # maps of buffers that no longer exist
-            del _POS_INVERSE[k]
-        cells, count = tables.pos_inverse(pos, ntab)
-        hit = (weakref.ref(pos), cells.to(pos.device), count)
-        _POS_INVERSE[key] = hit
-    return hit[1], hit[2]
-
-
-def wattn_bwd(qkv, o, dout, lse, rel_pos, pos, region, B, L, n_head, swin, ntab, defer=False, use_inverse=True):
-    """-> dqkv, drel_pos [ntab, n_head] -- or with ``defer`` (dqkv, Partials) for a later colreduce_multi.
-    ``use_inverse=False`` (tests) takes the kernel's LDS-atomic scatter of the rel_pos gradient instead of the gather over
-    the inverse pos map."""
-    _dev(qkv, o, dout, lse, rel_pos, pos, region)
-    lib = _lib.load()
-    inv_cells, inv_count = _pos_inverse(pos, ntab) if use_inverse else (None, 0)
-    H, W, win, shift = swin
-    dqkv = torch.empty_like(qkv)
-    drel = None if defer else torch.empty((ntab, n_head), dtype=torch.float32, device=qkv.device)
-    wsb = lib.vtx_wattn_bwd_workspace(B, n_head, H, W, win)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=qkv.device)
-    nW = (H // win) * (W // win)
-    tn = "__bf16" if qkv.dtype == torch.bfloat16 else "float"
-    ev = _attn_bracket(wattn_bwd_kernel_name(qkv.dtype, region is not None, use_inverse), B * nW * n_head, L, 32,
-                       B * nW * L, n_head * 32, qkv.element_size(), True)     # (+ the small drel_pos column reduce)
-    check(lib.vtx_wattn_bwd(_p(qkv), _p(o), _p(dout), _p(lse), _p(rel_pos), _p(pos), _p(region), _p(dqkv), _p(drel),
-                            _p(ws), wsb, _p(inv_cells), inv_count, B, L, n_head, H, W, win, int(bool(shift)), _dt(qkv),
-                            _stream()),
-          "vtx_wattn_bwd")
-    if ev:
-        ev[1].record()
-    if defer:
-        return dqkv, Partials(ws, lib.vtx_wattn_bwd_parts(B, n_head, H, W, win), ntab * n_head, lib.vtx_wattn_bwd_part_ld(n_head), False)
-    return dqkv, drel
+# ------------------------------------------------------------------------------- attention: vtx/attention.py, reached through this module
+from .attention import (SHORT_MAX, _drop_args, _pos_inverse, _sattn_cfg, attention_bwd, attention_fwd, attn_hd_bwd,        # noqa: E402,F401
+                        attn_hd_fwd, attn_hd_pad, attn_hd_routes, attn_hd_supported, attn_hdw_bwd, attn_hdw_fwd, attn_hdw_routes,
+                        attn_keep_mask, generic_label, pos_csr, relpos_bias, srattn_bwd, srattn_fwd, srattn_scores, table_bias,
+                        table_bias_bwd, wattn_bwd, wattn_bwd_kernel_name, wattn_fwd, wattn_fwd_kernel_name, wattn_supported,
+                        window_gather, window_scatter, xattn_bwd, xattn_fwd)
