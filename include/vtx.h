@@ -878,13 +878,33 @@ int vtx_cls_metrics(const void* logits, const int64_t* labels, float* ce_rows, i
  *   meter [1 + 2 nk] fp64 or NULL: [n, top1_ks0, top5_ks0, top1_ks1, top5_ks1, ...]; the call ADDS M and the rows with
  *   rank < 1 and with rank < min(5, ks[i]).  One workgroup, fixed summation order, no atomics.
  *   Errors: VTX_ERR_NULL (any pointer but meter), VTX_ERR_SHAPE (M, N < 1 or >= 2^31; L outside 1..256; C < 1; nk outside
- *   1..8; ks[i] outside 1..L; T not > 0). */
+ *   1..8; ks[i] outside 1..L; T not > 0).
+ *
+ * vtx_knn_merge_lists: the search over a bank of N rows that is cut into nlist (1..64) shards of consecutive rows, one per
+ *   rank: every shard was searched on its own (vtx_knn_topk with k_s = min(k, rows of the shard)) and the lists meet here.
+ *   lens, bases: HOST arrays of nlist values, copied into the launch (no device copy, no synchronisation): list s holds
+ *   lens[s] (0..k) real pairs in order, its indices are local to shard s, whose row 0 is row bases[s] of the bank.
+ *   List s of query m starts at element m * row_stride + s * list_stride of lval / lidx; places at or beyond lens[s] are
+ *   never read.  Two layouts through the one entry: rank-major, as a gather of the ranks' [rows, k] results leaves them
+ *   (list_stride = rows * k, row_stride = k, the pointers advanced to the caller's first query), and query-major, as the
+ *   split workspace of vtx_knn_topk (row_stride = nlist * k, list_stride = k).
+ *   val [M, k] fp32, idx [M, k] int32: the first k pairs of all lists in the order "higher score first, among equal scores
+ *   the lower global index first", global index = bases[s] + local index.  Scores are pair-local, so this is bit for bit
+ *   the answer of vtx_knn_topk over the whole bank.  A NaN score orders as -inf; on lists that are not ordered the
+ *   neighbours are unspecified, and even then every written index lies in [0, N) and the call ends.
+ *   Errors, all before any launch: VTX_ERR_NULL (any pointer), VTX_ERR_SHAPE (M < 1 or >= 2^31; N < 1 or >= 2^31 - 1; nlist
+ *   outside 1..64; k outside 1..256; a lens[s] outside 0..k or above the rows of shard s = bases[s + 1] - bases[s], N -
+ *   bases[s] for the last; sum of lens < k; bases[0] < 0, bases decreasing, bases[nlist - 1] > N; list_stride < k with
+ *   nlist > 1; row_stride < k with M > 1). */
 size_t vtx_knn_workspace_bytes(int64_t M, int64_t N, int k, int splits);
 int vtx_knn_topk(const void* q, const void* f, float* val, int32_t* idx, int64_t M, int64_t N, int D, int k, int splits,
                  void* ws, size_t ws_bytes, int dtype, void* stream);
 int vtx_knn_vote(const float* val, const int32_t* idx, const int64_t* bank_labels, const int64_t* query_labels,
                  int32_t* rank, int32_t* pred, double* meter, const int32_t* ks, int nk, int64_t M, int L, int64_t N, int C,
                  float T, void* stream);
+int vtx_knn_merge_lists(const float* lval, const int32_t* lidx, float* val, int32_t* idx, const int32_t* lens,
+                        const int32_t* bases, int nlist, int64_t M, int k, int64_t row_stride, int64_t list_stride, int64_t N,
+                        void* stream);
 
 /* ---- Multi-tensor weight cast (csrc/cast.hip): all fp32 Linear / Conv weights of a model -> bf16, plain [out][in]
  * and transposed [in][out], in one launch per forward.  This is the per-call weight cast of the reference's bf16

@@ -19,6 +19,9 @@
 //                       (k / n of the scores at bank row n).
 //   knn_merge_kernel    splits > 1: every split wrote its k-list to the workspace; one workgroup per query row places
 //                       each of the splits * k pairs by counting the pairs before it (knn_merge_place).
+//   knn_merge_lists_kernel   the bank is cut over ranks: every shard found a ragged list with shard-local indices; one
+//                       workgroup per query row stages them in LDS and places each pair among all of them by global index
+//                       (knn_merge_place_lists).  Serves the rank-major layout of a gather and the workspace layout.
 //   knn_vote_kernel     one wave per query: w_i = expf(val_i / T), votes per class summed in neighbour order, the rank of
 //                       the query's label and the winning class for up to 8 values of k.
 //   knn_meter_kernel    one workgroup adds the batch to the fp64 meter in a fixed order (as cls_meter_accumulate_kernel).
@@ -34,7 +37,10 @@
 #define KNN_LDS_BYTES (160 * 1024)   // LDS of a CU: one workgroup may have all of it
 #define KNN_MAX_D 1024
 
+#define KNN_MAX_LISTS 64     // lists (shards) vtx_knn_merge_lists takes at most
+
 struct KnnKs { int k[8]; };
+struct KnnLists { int32_t len[KNN_MAX_LISTS]; int32_t base[KNN_MAX_LISTS]; };      // by value: 512 B of kernel argument
 
 // Keeps the compiler from moving one wave's LDS accesses across this point.  Nothing is waited for: the lanes of a wave run
 // in lockstep and LDS serves a wave's accesses in order.  (A fence would also wait for the bank tile's global loads that
@@ -255,6 +261,49 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const float* __restrict_
       if (i > N - 1) i = N - 1;                        // (never taken while the order is total: the range promise)
       val[m * k + place] = v[e];
       idx[m * k + place] = i;
+    }
+  }
+}
+
+// The ragged lists of query row m that the shards of a bank cut over ranks found (list s: len[s] ordered pairs with indices
+// local to a shard that starts at global row base[s]) -> the row's k-list with global indices.  One workgroup per query.
+// The lists are staged in LDS as [nlist][k] (scores cleaned on the way in, places past len[s] left unwritten and never
+// read) together with len and base: every pair is then read about nlist * log2(k) times by the binary searches of
+// knn_merge_place_lists, and the kernel argument is indexed by the thread id once, in the staging loop.
+__global__ __launch_bounds__(256) void knn_merge_lists_kernel(const float* __restrict__ lval, const int32_t* __restrict__ lidx,
+                                                             float* __restrict__ val, int32_t* __restrict__ idx,
+                                                             KnnLists lists, int nlist, int k, int64_t row_stride,
+                                                             int64_t list_stride, int N) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char knn_smem[];
+  __shared__ int32_t s_len[KNN_MAX_LISTS], s_base[KNN_MAX_LISTS];
+  float* sv = reinterpret_cast<float*>(knn_smem);                       // [nlist][k]
+  int32_t* si = reinterpret_cast<int32_t*>(sv + nlist * k);             // [nlist][k]
+  const int64_t m = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (tid < KNN_MAX_LISTS) {
+    s_len[tid] = tid < nlist ? lists.len[tid] : 0;
+    s_base[tid] = tid < nlist ? lists.base[tid] : 0;
+  }
+  __syncthreads();
+  const int total = nlist * k;
+  for (int e = tid; e < total; e += 256) {
+    const int s = e / k, p = e - s * k;
+    if (p < s_len[s]) {
+      const int64_t src = m * row_stride + s * list_stride + p;
+      sv[e] = knn_clean(lval[src]);
+      si[e] = lidx[src];
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < total; e += 256) {
+    const int s = e / k, p = e - s * k;
+    if (p >= s_len[s]) continue;
+    const int place = knn_merge_place_lists(sv, si, s_len, s_base, nlist, k, s, p);
+    if (place < k) {
+      int64_t g = (int64_t)s_base[s] + si[e];
+      g = g < 0 ? 0 : (g > N - 1 ? N - 1 : g);         // (never taken on the lists of a search: the range promise)
+      val[m * k + place] = sv[e];
+      idx[m * k + place] = (int32_t)g;
     }
   }
 }
@@ -491,6 +540,35 @@ int vtx_knn_topk(const void* q, const void* f, float* val, int32_t* idx, int64_t
   if (s > 1)
     hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)M), dim3(256), 0, st, (const float*)ov, (const int32_t*)oi, val, idx,
                        s, k, (int)N);
+  return vtx_check_launch();
+}
+
+/* include/vtx.h: vtx_knn_merge_lists */
+int vtx_knn_merge_lists(const float* lval, const int32_t* lidx, float* val, int32_t* idx, const int32_t* lens,
+                        const int32_t* bases, int nlist, int64_t M, int k, int64_t row_stride, int64_t list_stride, int64_t N,
+                        void* stream) {
+  if (!lval || !lidx || !val || !idx || !lens || !bases) return VTX_ERR_NULL;
+  if (M < 1 || M >= (1ll << 31) || N < 1 || N >= (1ll << 31) - 1 || nlist < 1 || nlist > KNN_MAX_LISTS || k < 1 ||
+      k > KNN_MAX_K)
+    return VTX_ERR_SHAPE;
+  KnnLists L;
+  int64_t sum = 0;
+  for (int s = 0; s < KNN_MAX_LISTS; ++s) {
+    L.len[s] = 0; L.base[s] = 0;
+    if (s >= nlist) continue;
+    const int64_t lo = bases[s], hi = s + 1 < nlist ? (int64_t)bases[s + 1] : N;      // shard s holds global rows [lo, hi)
+    if (lo < 0 || hi < lo || lens[s] < 0 || lens[s] > k || (int64_t)lens[s] > hi - lo) return VTX_ERR_SHAPE;
+    L.len[s] = lens[s]; L.base[s] = bases[s];
+    sum += lens[s];
+  }
+  if (sum < k) return VTX_ERR_SHAPE;
+  if ((nlist > 1 && list_stride < k) || (M > 1 && row_stride < k)) return VTX_ERR_SHAPE;
+  const size_t smem = (size_t)nlist * k * 8;           // <= 128 KiB
+  if (smem + 512 > 64 * 1024 && hipFuncSetAttribute((const void*)knn_merge_lists_kernel,      // (+ the 512 B of len / base)
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+    return VTX_ERR_LAUNCH;
+  hipLaunchKernelGGL(knn_merge_lists_kernel, dim3((unsigned)M), dim3(256), smem, (hipStream_t)stream, lval, lidx, val, idx, L,
+                     nlist, k, row_stride, list_stride, (int)N);
   return vtx_check_launch();
 }
 

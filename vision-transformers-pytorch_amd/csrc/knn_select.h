@@ -72,3 +72,35 @@ KNN_HD int knn_merge_place(const float* val, const int32_t* idx, int nlist, int 
     if (t != s) place += knn_count_before(val + t * k, idx + t * k, k, cv, ci);
   return place;
 }
+
+// ---- lists of the shards of a bank that is cut over ranks (vtx_knn_merge_lists)
+// `nlist` RAGGED lists: list t holds lens[t] (0 .. k) real pairs in order at val + t * list_stride / idx + t * list_stride,
+// and its indices are local to a shard whose row 0 is row bases[t] of the whole bank.  The order is the one above on
+// (score, GLOBAL index = bases[t] + idx): higher score first, among equal scores the lower global index first.  Places at
+// or beyond lens[t] are never read -- there are no sentinels to rely on, a list says how long it is.  Scores go through
+// knn_clean as they are read (a NaN orders as -inf); the global index is formed in 64 bits, so that no input overflows it.
+
+KNN_HD bool knn_before_global(float av, int64_t ag, float bv, int64_t bg) { return av > bv || (av == bv && ag < bg); }
+
+// Number of the `len` pairs of an ordered list of shard `base` that come before (cv, cg): binary search, <= 9 steps.
+KNN_HD int knn_count_before_global(const float* val, const int32_t* idx, int len, int32_t base, float cv, int64_t cg) {
+  int lo = 0, hi = len;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (knn_before_global(knn_clean(val[mid]), (int64_t)base + idx[mid], cv, cg)) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// Place of pair p (< lens[s]) of list s in the merged order: the pairs before it in its own list (p) plus those before
+// it in every other list.  Shards hold disjoint global rows, so the order is strict and the places 0 .. sum(lens) - 1 are
+// taken once each; the pair belongs to the answer when its place is < k.
+KNN_HD int knn_merge_place_lists(const float* val, const int32_t* idx, const int32_t* lens, const int32_t* bases, int nlist,
+                                 int64_t list_stride, int s, int p) {
+  const float cv = knn_clean(val[s * list_stride + p]);
+  const int64_t cg = (int64_t)bases[s] + idx[s * list_stride + p];
+  int place = p;
+  for (int t = 0; t < nlist; ++t)
+    if (t != s) place += knn_count_before_global(val + t * list_stride, idx + t * list_stride, lens[t], bases[t], cv, cg);
+  return place;
+}

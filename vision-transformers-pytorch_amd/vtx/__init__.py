@@ -9,10 +9,12 @@
   vtx.ddp         data-parallel gradient all-reduce over RCCL on a side stream
   vtx.optim       FusedAdamW (clip + AdamW + model EMA in one pass), ModelEma; vtx.accumulate = train_util.accumulate
   vtx.knn         weighted k-NN evaluation of frozen features: FeatureBank, knn_search, KnnMeter, extract_features,
-                  knn_evaluate (also reachable as vtx.FeatureBank, ...)
+                  knn_evaluate; ShardedFeatureBank, knn_search_sharded for a bank cut over ranks (also reachable as
+                  vtx.FeatureBank, ...)
 """
 
-_KNN_NAMES = ("FeatureBank", "KnnMeter", "knn_search", "extract_features", "knn_evaluate")
+_KNN_NAMES = ("FeatureBank", "KnnMeter", "knn_search", "extract_features", "knn_evaluate", "ShardedFeatureBank",
+              "knn_search_sharded")
 
 
 def __getattr__(name):

@@ -286,6 +286,8 @@ _SIGNATURES = {
                              c_size_t, c_int, c_void_p]),
     "vtx_knn_vote": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                              c_int64, c_int, c_int64, c_int, c_float, c_void_p]),
+    "vtx_knn_merge_lists": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
+                                    c_int64, c_int64, c_int64, c_void_p]),
     "vtx_cast_desc_bytes": (c_size_t, []),
     "vtx_cast_weights": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vtx_patch_gather": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -14,12 +14,16 @@ the vote of a class is summed in neighbour order in fp32; a label is a hit at to
 it in a STABLE descending sort of the votes (classes without a neighbour have vote 0 and take part).  ``torch.topk``
 leaves ties unspecified; everywhere else the numbers are those of the usual torch formulation (mm, topk, scatter_add).
 
-Not in scope: every process holds its own WHOLE bank.  Gathering a bank that is sharded over ranks is not part of this
-module; ``KnnMeter.all_reduce`` only sums the counts of ranks that metered different queries against the same bank.
+A bank may stay where it was extracted: ``ShardedFeatureBank`` holds this rank's rows only, ``seal()`` tells every rank
+the shards' sizes and all labels, and ``knn_search_sharded`` gathers the ranks' queries, searches them against the local
+shard and merges the gathered lists by global index (vtx_knn_merge_lists).  The order is total and the scores are
+pair-local, so the result is bit for bit that of ``knn_search`` over the whole bank.  ``KnnMeter.all_reduce`` sums the counts
+of ranks that metered different queries, against a whole bank each or against a sharded one.
 """
 import ctypes
 
 import torch
+import torch.distributed as dist
 
 from . import ops
 from .ops import VtxError
@@ -114,6 +118,123 @@ def knn_search(queries, bank_features, k, splits=0):
     return val, idx
 
 
+def _world(group):
+    """(world size, rank) of ``group``; (1, 0) where torch.distributed does not run."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return 1, 0
+    return dist.get_world_size(group), dist.get_rank(group)
+
+
+def _gather(out, src, group):
+    """out [R, ...] <- the ``src`` of every rank, in rank order: ONE all_gather into the R views of the preallocated ``out``
+    (every backend; there is no all_to_all or reduce_scatter for device tensors under gloo)."""
+    dist.all_gather(list(out.unbind(0)), src, group=group)
+
+
+class ShardedFeatureBank(FeatureBank):
+    """This rank's part of a bank that is cut over the ranks of ``group``: ``capacity`` and ``add`` are per rank, the rows
+    stay where they were extracted.  Global row index = ``bases[rank]`` + local index, ranks in order.
+
+    ``seal()`` ends the fill, once per bank: one gather of the row counts and one of the labels (padded to the largest
+    count, then compacted) set ``counts`` and ``bases`` (host ints, exclusive prefix sum), ``global_len`` and
+    ``global_labels`` (int64 [global_len] on every rank -- 10 MB for ImageNet -- so that the vote runs unchanged).  It may
+    synchronise the host.  ``add`` after ``seal`` and a search before it raise VtxError; ``reset`` unseals.  Shards may be
+    ragged, empty, or shorter than k.  Without a process group, or with one rank, it is a plain bank: ``seal`` is local and
+    the search is ``knn_search``."""
+
+    def __init__(self, dim, capacity, dtype=torch.bfloat16, device="cuda", group=None):
+        super().__init__(dim, capacity, dtype, device)
+        self.group = group
+        self._unseal()
+
+    def _unseal(self):
+        self.sealed = False
+        self.counts = self.bases = self.global_len = self.global_labels = None
+
+    def reset(self):
+        super().reset()
+        self._unseal()
+
+    def add(self, features, labels):
+        if self.sealed:
+            raise VtxError("vtx: ShardedFeatureBank.add after seal(); reset() starts a new bank")
+        super().add(features, labels)
+
+    def seal(self):
+        world, rank = _world(self.group)
+        n = len(self)
+        if world <= 1:
+            counts, labels = [n], self.labels
+        else:
+            allc = torch.empty((world, 1), dtype=torch.int64, device=self.device)
+            _gather(allc, torch.tensor([n], dtype=torch.int64, device=self.device), self.group)
+            counts = [int(c) for c in allc.view(-1).tolist()]          # (a host synchronisation, once per bank)
+            most = max(counts)
+            if most > 0:
+                mine = torch.zeros((most,), dtype=torch.int64, device=self.device)
+                mine[:n].copy_(self.labels)
+                alll = torch.empty((world, most), dtype=torch.int64, device=self.device)
+                _gather(alll, mine, self.group)
+                labels = torch.cat([alll[r, :c] for r, c in enumerate(counts)])
+            else:
+                labels = self.labels
+        if sum(counts) >= 2 ** 31 - 1:
+            raise VtxError(f"vtx: a bank of {sum(counts)} rows does not fit int32 indices")
+        self.counts = counts
+        self.bases = [sum(counts[:r]) for r in range(world)]
+        self.global_len = sum(counts)
+        self.global_labels = labels
+        self.sealed = True
+        return self
+
+
+def knn_search_sharded(queries, bank, k, splits=0):
+    """``knn_search`` of this rank's ``queries`` (already normalised, [M, dim] of the bank's dtype) over ALL shards of a
+    sealed ``ShardedFeatureBank``: (val fp32 [M, k], idx int32 [M, k]) with GLOBAL indices, bit-equal to the search over
+    the whole bank.  The caller's contract: every rank of the bank's group calls with the same M (DistributedSampler pads
+    to that) and the same k.
+
+    One gather of the queries (every rank then holds all R M rows), the search of those rows against the local shard with
+    k_local = min(k, rows of the shard) into [R M, k] buffers (skipped for an empty shard), one gather each of the scores
+    and the indices, and vtx_knn_merge_lists over this rank's M rows of the R gathered lists.  No host synchronisation:
+    the shards' sizes are the host numbers of ``seal()``.  Refuses before any collective when k > ``global_len``."""
+    if not isinstance(bank, ShardedFeatureBank):
+        raise VtxError("vtx: knn_search_sharded needs a ShardedFeatureBank (knn_search takes a plain bank's features)")
+    if not bank.sealed:
+        raise VtxError("vtx: knn_search_sharded before ShardedFeatureBank.seal()")
+    k = int(k)
+    if k < 1 or k > 256 or k > bank.global_len:
+        raise VtxError(f"vtx: the bank holds {bank.global_len} rows over all ranks; k = {k} must be in 1..min(256, that)")
+    if not torch.is_tensor(queries) or not queries.is_cuda or queries.dim() != 2:
+        raise VtxError("vtx: knn_search_sharded needs a 2-D device tensor for the queries (there is no CPU fallback)")
+    if queries.shape[1] != bank.dim or queries.dtype != bank.dtype or queries.shape[0] < 1:
+        raise VtxError(f"vtx: knn_search_sharded takes (M, {bank.dim}) {bank.dtype} queries, got {tuple(queries.shape)} "
+                       f"{queries.dtype}")
+    world = len(bank.counts)
+    if world <= 1:
+        return knn_search(queries, bank.features, k, splits)
+    rank = dist.get_rank(bank.group)
+    q = queries if queries.is_contiguous() else queries.contiguous()
+    M, D = q.shape
+    allq = torch.empty((world, M, D), dtype=q.dtype, device=q.device)
+    _gather(allq, q, bank.group)
+    k_local = min(k, len(bank))
+    if k_local == k:
+        mine_v, mine_i = knn_search(allq.view(world * M, D), bank.features, k, splits)
+    else:                                              # a short shard: its lists fill the first k_local places
+        mine_v = torch.empty((world * M, k), dtype=torch.float32, device=q.device)
+        mine_i = torch.empty((world * M, k), dtype=torch.int32, device=q.device)
+        if k_local > 0:
+            v, i = knn_search(allq.view(world * M, D), bank.features, k_local, splits)
+            mine_v[:, :k_local].copy_(v)
+            mine_i[:, :k_local].copy_(i)
+    lv = torch.empty((world, world * M, k), dtype=torch.float32, device=q.device)
+    li = torch.empty((world, world * M, k), dtype=torch.int32, device=q.device)
+    _gather(lv, mine_v, bank.group)
+    _gather(li, mine_i, bank.group)
+    return ops.knn_merge_lists(lv, li, [min(k, c) for c in bank.counts], bank.bases, k, bank.global_len, rank * M, M)
+
+
 class KnnMeter:
     """Counts of a weighted k-NN evaluation on the device: ``[n, top1_k0, top5_k0, top1_k1, ...]`` as float64.
 
@@ -141,7 +262,9 @@ class KnnMeter:
 
     def update(self, queries, labels, bank, splits=0):
         """Add a batch: (B, dim) device features (normalised here, cast to the bank's dtype), (B,) integer device labels,
-        a ``FeatureBank`` that holds at least max(ks) rows.  -> (rank int32 [B, nk], pred int32 [B, nk])."""
+        a ``FeatureBank`` that holds at least max(ks) rows.  -> (rank int32 [B, nk], pred int32 [B, nk]).
+        A sealed ``ShardedFeatureBank`` is searched over all its shards (``knn_search_sharded``: every rank calls with the
+        same B) and voted against its ``global_labels``."""
         if not torch.is_tensor(queries) or not queries.is_cuda or queries.dim() != 2 or not queries.is_floating_point():
             raise VtxError("vtx: KnnMeter.update needs (B, dim) floating-point features on the GPU (no CPU fallback)")
         if not torch.is_tensor(labels) or not labels.is_cuda or labels.dim() != 1 or labels.numel() != queries.shape[0] \
@@ -149,6 +272,11 @@ class KnnMeter:
             raise VtxError(f"vtx: KnnMeter.update needs {queries.shape[0]} integer labels on the GPU")
         if not isinstance(bank, FeatureBank) or queries.shape[1] != bank.dim:
             raise VtxError("vtx: KnnMeter.update needs a FeatureBank of the queries' width")
+        if isinstance(bank, ShardedFeatureBank):       # all shards, global indices; refuses an unsealed or too small bank
+            q, _ = ops.l2norm_fwd(queries.detach().to(bank.dtype).contiguous(), 1e-12)
+            val, idx = knn_search_sharded(q, bank, max(self.ks), splits)
+            return ops.knn_vote(val, idx, bank.global_labels, labels.contiguous(), self._ks, self.n_class, self.T,
+                                self._tensor())
         if len(bank) < max(self.ks):
             raise VtxError(f"vtx: the bank holds {len(bank)} rows, fewer than k = {max(self.ks)}")
         q, _ = ops.l2norm_fwd(queries.detach().to(bank.dtype).contiguous(), 1e-12)
@@ -202,10 +330,16 @@ def extract_features(model, loader, bank, feature_fn=None, autocast_dtype=torch.
 
 
 def knn_evaluate(model, train_loader, valid_loader, bank=None, capacity=None, ks=(10, 20, 100, 200), T=0.07, n_class=1000,
-                 feature_fn=None, autocast_dtype=torch.bfloat16, dtype=torch.bfloat16, device="cuda", group=None):
+                 feature_fn=None, autocast_dtype=torch.bfloat16, dtype=torch.bfloat16, device="cuda", group=None,
+                 sharded=False):
     """Weighted k-NN accuracy of ``model``'s frozen features: a bank from ``train_loader`` (``capacity`` rows, by default
     ``len(train_loader.dataset)``; or a filled ``bank`` to reuse, then ``train_loader`` may be None), every batch of
-    ``valid_loader`` metered against it, ONE all-reduce of the counts, the model's mode restored.  -> KnnMeter.compute()."""
+    ``valid_loader`` metered against it, ONE all-reduce of the counts, the model's mode restored.  -> KnnMeter.compute().
+
+    ``sharded=True``: ``train_loader`` yields this rank's part of the training set only; the rows go into a
+    ``ShardedFeatureBank`` over ``group`` (``capacity`` per rank, by default ceil(len(dataset) / world)) that is sealed after
+    the extraction, and every rank's queries are searched over all shards (every rank must then meter batches of the same
+    sizes, see ``knn_search_sharded``).  A sampler that pads the ranks to one length repeats at most world - 1 bank rows."""
     meter = KnnMeter(ks, T, n_class, device)
     was_training = model.training
     model.eval()
@@ -216,11 +350,18 @@ def knn_evaluate(model, train_loader, valid_loader, bank=None, capacity=None, ks
             elif bank is None:                        # the first batch tells the feature width
                 if capacity is None:
                     capacity = len(train_loader.dataset)
+                    if sharded:
+                        capacity = max(1, -(-capacity // _world(group)[0]))
                 for x, label in train_loader:
                     feat = _features_of(model, x.to(meter.device, non_blocking=True), feature_fn, autocast_dtype)
                     if bank is None:
-                        bank = FeatureBank(feat.shape[-1], capacity, dtype, device)
+                        bank = ShardedFeatureBank(feat.shape[-1], capacity, dtype, device, group) if sharded \
+                            else FeatureBank(feat.shape[-1], capacity, dtype, device)
                     bank.add(feat, label.to(meter.device, non_blocking=True))
+                if bank is None and sharded:
+                    raise VtxError("vtx: knn_evaluate got no batch from train_loader; pass a bank for an empty shard")
+            if isinstance(bank, ShardedFeatureBank) and not bank.sealed:
+                bank.seal()
             for x, label in valid_loader:
                 x = x.to(meter.device, non_blocking=True)
                 meter.update(_features_of(model, x, feature_fn, autocast_dtype), label.to(meter.device, non_blocking=True), bank)

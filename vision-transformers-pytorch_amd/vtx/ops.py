@@ -1525,6 +1525,38 @@ def knn_topk(q, f, k, splits=0):
     return val, idx
 
 
+def knn_merge_lists(lval, lidx, lens, bases, k, N, row0=0, rows=None):
+    """The k-lists of ``rows`` queries over a bank of ``N`` rows that is cut into shards, from the shards' own lists:
+    ``lval`` fp32 / ``lidx`` int32 of shape [nlist, rows_total, k] with a unit last stride (the rank-major block a gather
+    leaves is contiguous; the query-major split workspace [M, nlist, k] goes in as ``.permute(1, 0, 2)``), list s holding
+    ``lens[s]`` ordered pairs with indices local to the shard that starts at global row ``bases[s]`` (host ints).  Queries
+    ``row0 .. row0 + rows`` are merged (default: all from row0).  -> (val fp32 [rows, k], idx int32 [rows, k], global
+    indices), bit-equal to knn_topk over the whole bank; rules and limits: include/vtx.h."""
+    for t in (lval, lidx):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise VtxError("vtx: the HIP path needs device tensors (there is no CPU fallback)")
+    k = int(k)
+    if lval.dim() != 3 or lval.shape != lidx.shape or lval.stride() != lidx.stride() or lval.dtype != torch.float32 \
+            or lidx.dtype != torch.int32 or lval.shape[2] != k or lval.stride(2) != 1:
+        raise VtxError("vtx: knn_merge_lists takes an fp32 / int32 pair of [nlist, rows, k] lists of one layout")
+    nlist, total = lval.shape[0], lval.shape[1]
+    row0 = int(row0)
+    rows = total - row0 if rows is None else int(rows)
+    if row0 < 0 or rows < 1 or row0 + rows > total or len(lens) != nlist or len(bases) != nlist:
+        raise VtxError(f"vtx: knn_merge_lists: rows {row0}..{row0 + rows} of {total}, {len(lens)} lens / {len(bases)} bases "
+                       f"for {nlist} lists")
+    ll = lens if isinstance(lens, ctypes.Array) else (ctypes.c_int32 * nlist)(*[int(v) for v in lens])
+    bb = bases if isinstance(bases, ctypes.Array) else (ctypes.c_int32 * nlist)(*[int(v) for v in bases])
+    list_stride, row_stride = lval.stride(0), lval.stride(1)
+    val = torch.empty((rows, k), dtype=torch.float32, device=lval.device)
+    idx = torch.empty((rows, k), dtype=torch.int32, device=lval.device)
+    off = 4 * row0 * row_stride
+    with _timed("knn_merge_lists_kernel", 0.0, 8.0 * rows * (float(sum(ll)) + k)):
+        check(_lib.load().vtx_knn_merge_lists(lval.data_ptr() + off, lidx.data_ptr() + off, _p(val), _p(idx), ll, bb, nlist,
+                                              rows, k, row_stride, list_stride, int(N), _stream()), "vtx_knn_merge_lists")
+    return val, idx
+
+
 def knn_vote(val, idx, bank_labels, query_labels, ks, n_class, T, meter=None):
     """Weighted vote of a search result: w = expf(val / T), votes per class in neighbour order, the rank of every query's
     label and the winning class for each k of ``ks`` (ints or a prepared ``ctypes.c_int32`` array); with ``meter`` (float64
