@@ -906,6 +906,61 @@ int vtx_knn_merge_lists(const float* lval, const int32_t* lidx, float* val, int3
                         const int32_t* bases, int nlist, int64_t M, int k, int64_t row_stride, int64_t list_stride, int64_t N,
                         void* stream);
 
+/* ---- Linear-probe evaluation of frozen features (csrc/probe.hip): H linear heads (1..32), one per (learning rate,
+ * weight decay) pair, trained at once on rows of a feature bank.  The (rows, classes) logit matrix is never written.
+ * No host synchronisation, no global state, no floating-point atomics: the same inputs give the same bits.
+ *
+ * Common layouts: x [N, D] of dtype (bf16 or fp32), rows used as given; rows: int32 [M] indices into x and labels, or NULL
+ * for rows 0..M-1 (repeats are allowed; an index outside [0, N) is clamped into it, never used as given); labels [N]
+ * int64; w [H, C, D] of dtype; bias [H, C] fp32 or NULL.  D is a multiple of 8 in 8..1024, C >= 1, 1 <= M <= N < 2^31.
+ *
+ * vtx_probe_fwd: lse, ce [H, M] fp32, pred [H, M] int32, meter [H, 3] fp64 or NULL.
+ *   - Pair-local logits.  The logit of (row, class) is the fp32-accumulated dot product of the two rows -- one MFMA chain
+ *     over D for every pair (v_mfma_f32_16x16x32_bf16, or the exact 16x16x4_f32 chain in fp32) -- followed by one fp32 add
+ *     of the bias.  It depends on its two rows and the bias only: not on M, H, the head's index, rows or the tile the
+ *     pair falls in.  The same pair gives the same bits in every call, and the backward recomputes the same bits.
+ *   - lse = max + __logf(sum), from a running maximum and a rescaled running sum of __expf(logit - max) over the classes in
+ *     ascending order; pad classes of the last class tile add nothing to the sum and are never a candidate.
+ *   - ce = lse - logit of the label.
+ *   - pred = the first class of the highest logit: among equal logits the lower class index wins -- the rule of
+ *     vtx_cls_metrics, so pred == label exactly when rank < 1 there.
+ *   - A label outside [0, C) is never used as an index: ce = NaN, the row is counted and never a hit.
+ *   - A NaN logit gives ce = NaN and a pred that is unspecified but inside [0, C).
+ *   - meter[h] = [n, loss_sum, top1]: a second launch ADDS M, the sum of ce over the rows whose label is a class and the
+ *     rows with pred == label.  One workgroup, fixed summation order, no atomics.
+ *   Errors, all before any launch: VTX_ERR_NULL (x, labels, w, lse, ce, pred), VTX_ERR_SHAPE (M < 1, M > N, N >= 2^31, H
+ *   outside 1..32, C < 1, H * C * D >= 2^31, D > 1024), VTX_ERR_ALIGN (D % 8 != 0; x or w not 16-byte aligned),
+ *   VTX_ERR_DTYPE.
+ *
+ * vtx_probe_bwd: lse [H, M] of the forward; dw [H, C, D] fp32, db [H, C] fp32 (written, not added to).
+ *   g = (__expf(logit - lse_row) - [c == label_row]) * scale in fp32 on the recomputed logits (a label outside [0, C)
+ *   matches no class); dw[h, c, :] = sum over the rows of g x_row through a second MFMA, g rounded to bf16 (round to nearest
+ *   even) on the way in bf16 mode; db[h, c] = sum of the unrounded g.  dX is not computed: the features are frozen.
+ *   Rows are cut into slabs that fill the chip; the slab count is a function of (M, H, C, D) alone, the slabs' partials go
+ *   to the workspace and are reduced in a fixed slab order: ascending.  vtx_probe_workspace_bytes(M, H, C, D) = slabs *
+ *   (H C D + H C) * 4 bytes, 0 for one slab; ws may be NULL when that is 0.
+ *   Errors: as the forward, and VTX_ERR_NULL (lse, dw, db; ws when a workspace is needed), VTX_ERR_SHAPE (scale not finite
+ *   or not > 0), VTX_ERR_WORKSPACE (ws_bytes short).
+ *
+ * vtx_probe_sgd: one launch over all heads, torch.optim.SGD semantics (dampening 0, no Nesterov, buffers zero at the start):
+ *     d = g + wd_h * w;   buf = mu * buf + d;   w = w - lr_h * buf
+ *   on the fp32 masters w [H, C, D] / b [H, C] with momentum buffers mw / mb and gradients dw / db; the bias takes the same
+ *   update with wd_h.  Contraction is off: every product and sum is rounded on its own in fp32, so a numpy float32
+ *   restatement gives the same bits.  lr, wd: HOST arrays of H floats, copied into the launch.  shadow [H, C, D] bf16 or
+ *   NULL: the round-to-nearest-even of the new master weights, written in the same pass (the w the next bf16 forward
+ *   reads); in fp32 mode the shadow is the master itself and the pointer is NULL.
+ *   Errors: VTX_ERR_NULL (any pointer but shadow), VTX_ERR_SHAPE (H outside 1..32, C < 1, D > 1024, H * C * D >= 2^31, mu
+ *   outside [0, 1), a negative or non-finite lr or wd), VTX_ERR_ALIGN (D % 8 != 0). */
+size_t vtx_probe_workspace_bytes(int64_t M, int H, int C, int D);
+int vtx_probe_fwd(const void* x, const int32_t* rows, const int64_t* labels, const void* w, const float* bias, float* lse,
+                  float* ce, int32_t* pred, double* meter, int64_t M, int64_t N, int H, int C, int D, int dtype,
+                  void* stream);
+int vtx_probe_bwd(const void* x, const int32_t* rows, const int64_t* labels, const void* w, const float* bias,
+                  const float* lse, float* dw, float* db, int64_t M, int64_t N, int H, int C, int D, float scale, void* ws,
+                  size_t ws_bytes, int dtype, void* stream);
+int vtx_probe_sgd(float* w, float* b, float* mw, float* mb, const float* dw, const float* db, void* shadow, const float* lr,
+                  const float* wd, float mu, int H, int C, int D, void* stream);
+
 /* ---- Multi-tensor weight cast (csrc/cast.hip): all fp32 Linear / Conv weights of a model -> bf16, plain [out][in]
  * and transposed [in][out], in one launch per forward.  This is the per-call weight cast of the reference's bf16
  * autocast (torch.cuda.amp.autocast around model(input), train.py:273-274) done once for the whole model.

@@ -11,10 +11,13 @@
   vtx.knn         weighted k-NN evaluation of frozen features: FeatureBank, knn_search, KnnMeter, extract_features,
                   knn_evaluate; ShardedFeatureBank, knn_search_sharded for a bank cut over ranks (also reachable as
                   vtx.FeatureBank, ...)
+  vtx.probe       linear-probe evaluation of frozen features: LinearProbe (many heads trained at once, fused linear +
+                  cross-entropy kernels), ProbeMeter, linear_probe_evaluate (also reachable as vtx.LinearProbe, ...)
 """
 
 _KNN_NAMES = ("FeatureBank", "KnnMeter", "knn_search", "extract_features", "knn_evaluate", "ShardedFeatureBank",
               "knn_search_sharded")
+_PROBE_NAMES = ("LinearProbe", "ProbeMeter", "linear_probe_evaluate")
 
 
 def __getattr__(name):
@@ -26,4 +29,7 @@ def __getattr__(name):
     if name in _KNN_NAMES:
         from . import knn
         return getattr(knn, name)
+    if name in _PROBE_NAMES:
+        from . import probe
+        return getattr(probe, name)
     raise AttributeError(f"module 'vtx' has no attribute {name!r}")

@@ -288,6 +288,13 @@ _SIGNATURES = {
                              c_int64, c_int, c_int64, c_int, c_float, c_void_p]),
     "vtx_knn_merge_lists": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
                                     c_int64, c_int64, c_int64, c_void_p]),
+    "vtx_probe_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
+    "vtx_probe_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
+    "vtx_probe_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                              c_int64, c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_int, c_void_p]),
+    "vtx_probe_sgd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_float, c_int, c_int, c_int, c_void_p]),
     "vtx_cast_desc_bytes": (c_size_t, []),
     "vtx_cast_weights": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vtx_patch_gather": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
