@@ -961,6 +961,55 @@ int vtx_probe_bwd(const void* x, const int32_t* rows, const int64_t* labels, con
 int vtx_probe_sgd(float* w, float* b, float* mw, float* mb, const float* dw, const float* db, void* shadow, const float* lr,
                   const float* wd, float mu, int H, int C, int D, void* stream);
 
+/* ---- Attention maps and per-head attention statistics (csrc/attention_maps.hip): read-only inspection of global attention.
+ * The reference's attention probabilities are an ordinary tensor (models/vit.py:36-39); here no kernel stores them, so these
+ * entries recompute them from the operands of vtx_attn_hd_fwd: q [B * Lq, nH * D] with row stride ldq, k [B * Lk, nH * D] with
+ * row stride ldkv (the packed QKV projection, or the q | kv pair of PVT / Twins), bf16 or fp32, D a multiple of 8 in 8..128, any
+ * Lq and Lk, scale = 1 / sqrt(D) formed as the attention kernels form it.  No bias, no mask, no windows.  No floating-point
+ * atomics; the same inputs give the same bits.
+ *
+ * Scores: s = acc * scale, acc the MFMA chain of the attention kernels (v_mfma_f32_16x16x32_bf16, or the exact 16x16x4_f32 chain
+ * in fp32; fp32 accumulation), one fp32 multiply.  Both score entries take the row maximum m in a first pass over the keys and
+ * every sum against that final m in a second (K is re-read from L2; nothing is rescaled), each of a query's four lanes summing
+ * its keys in ascending order and the four meeting in one fixed butterfly -- the term-by-term arithmetic is in the header comment
+ * of csrc/attention_maps.hip.  A row's outputs are the same bits however the rows are cut into calls, however the batch is cut,
+ * and whether the operand is the packed projection or a copy split into q and k.
+ *
+ * vtx_attn_map_rows: query rows row0 .. row0 + nrows - 1 of every image and head.  p fp32 [B, nH, nrows, Lk] = __expf(s - m) / l
+ *   with l the row sum of __expf(s - m); lse fp32 [B, nH, nrows] = m + __logf(l).  row0 = 0, nrows = 1: the CLS map; row0 = 0,
+ *   nrows = Lq: the whole P.
+ * vtx_attn_map_stats: stats fp32 [B, nH, Lq, 5] per query row i, P never written:
+ *     [0] lse                                                   bit-equal to the lse of vtx_attn_map_rows for that row
+ *     [1] entropy = lse - (sum_j e_j s_j) / l                   in nats; e_j = __expf(s_j - m)
+ *     [2] smax = m                                              the largest scaled logit, exact
+ *     [3] prefix = (sum_{j < n_prefix} e_j) / l                 the mass on the CLS / prefix keys
+ *     [4] dist = (sum_{j >= n_prefix} e_j |pos_i - pos_j|) / l  in patch units; token t >= n_prefix sits at ((t - n_prefix) / gw,
+ *         (t - n_prefix) % gw); |.| is v_sqrt_f32 of the exact integer dy^2 + dx^2.  Mass on prefix keys counts as distance 0; a
+ *         prefix query row stores 0; gh = gw = 0 switches dist off (0 is stored).  Keys and queries share the grid: gh * gw must
+ *         equal Lk - n_prefix and Lq - n_prefix, so the q | kv pair of a sub-sampled attention runs with gh = gw = 0.
+ * vtx_attn_map_meter: adds a stats tensor to meter fp64 [n_layer, nH, 6] at `layer`, one workgroup, fixed order: per head
+ *   [queries, sum entropy, sum prefix, sum dist over the patch queries (i >= n_prefix), patch queries, max smax].  The last is a
+ *   running maximum: the caller initialises it to -inf.  layer < n_layer is the caller's to keep.
+ * vtx_attn_mass_mask: the thresholding of DINO's attention visualisation on n_maps fp32 maps of n <= 4096 values (below zero or
+ *   NaN: counted as 0).  Sort ascending by (value, index): among equal values the lower index first.  The running sum in that
+ *   order, in fp32, in chunks of 16 sorted elements: inside chunk c left to right, w[c][0] = v[16 c], w[c][i] = w[c][i - 1] +
+ *   v[16 c + i]; P[0] = 0, P[c] = P[c - 1] + w[c - 1][15]; run[16 c + i] = P[c] + w[c][i]; total = run[n - 1];
+ *   thr = (1.f - keep) * total in fp32.  Element e gets byte 1 iff run at its sorted position > thr, else 0: a sum that hits thr
+ *   exactly is not kept and an all-zero map keeps nothing.  DINO's script divides by the total before the running sum; this
+ *   does not: the only difference.
+ *
+ * Errors, all before any launch, with the codes of the vtx_attn_hd entries: VTX_ERR_NULL (any pointer), VTX_ERR_DTYPE,
+ * VTX_ERR_SHAPE (B, Lq, Lk, nH, nrows, n_maps or n < 1; D outside the multiples of 8 in 8..128; B * Lq or B * Lk >= 2^31 - 1;
+ * row0 < 0 or row0 + nrows > Lq; a stride below nH * D; n_prefix outside 0..min(Lq, Lk); gh, gw not both 0 and gh * gw !=
+ * Lk - n_prefix or != Lq - n_prefix; layer < 0; n > 4096; keep outside (0, 1]), VTX_ERR_ALIGN (a stride that is not a multiple of
+ * 8; q or k off 16 bytes; an fp32 pointer off 4, the meter off 8). */
+int vtx_attn_map_rows(const void* q, const void* k, int64_t ldq, int64_t ldkv, float* p, float* lse, int B, int Lq, int Lk, int nH,
+                      int D, int row0, int nrows, int dtype, void* stream);
+int vtx_attn_map_stats(const void* q, const void* k, int64_t ldq, int64_t ldkv, float* stats, int B, int Lq, int Lk, int nH, int D,
+                       int n_prefix, int gh, int gw, int dtype, void* stream);
+int vtx_attn_map_meter(const float* stats, double* meter, int layer, int B, int nH, int Lq, int n_prefix, void* stream);
+int vtx_attn_mass_mask(const float* maps, uint8_t* mask, int n_maps, int n, float keep, void* stream);
+
 /* ---- Multi-tensor weight cast (csrc/cast.hip): all fp32 Linear / Conv weights of a model -> bf16, plain [out][in]
  * and transposed [in][out], in one launch per forward.  This is the per-call weight cast of the reference's bf16
  * autocast (torch.cuda.amp.autocast around model(input), train.py:273-274) done once for the whole model.

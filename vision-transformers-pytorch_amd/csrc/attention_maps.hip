@@ -1,0 +1,421 @@
+// Read-only inspection of global attention: rows of P = softmax(q k^T / sqrt(D)), per-query attention statistics without writing P, a
+// per-(layer, head) fp64 meter over them, and the mass threshold of DINO's attention visualisation.  In the reference the attention
+// probabilities are an ordinary tensor (models/vit.py:36-39) that a hook can read; here no kernel stores them, so these entries
+// recompute them from the operands the attention kernels take.
+//
+// Operands as vtx_attn_hd_fwd (csrc/attention_hd.hip): q [B * Lq, nH * D] with row stride ldq, k [B * Lk, nH * D] with row stride
+// ldkv -- the packed QKV projection (ldq = ldkv = 3 nH D) or the q | kv pair of PVT / Twins -- bf16 or fp32, D any multiple of 8 in
+// 8..128 (templated on the padded width DP in {32, 64, 96, 128}; the PADDING RULE of attention_hd.hip holds: a vector at d0 >= D is a
+// zero operand whose memory is never touched).  No bias, no mask, no windows.
+//
+// SCORES.  s(q, key) = acc * scale with acc the MFMA chain of hdattn_fwd_kernel -- one v_mfma_f32_16x16x32_bf16 per 32 columns in
+// bf16, eight v_mfma_f32_16x16x4_f32 per 32 columns (the exact fmaf chain) in fp32, fp32 accumulation -- and scale the fp32
+// 1.0f / sqrtf((float)D): ONE fp32 multiply.  A wave owns 16 queries; a product gives S^T[key][query]: lane (c = lane & 15,
+// g = lane >> 4) holds, for query c of the wave, the keys k0 + 16 kt + 4 g + r (kt, r in 0..3) of the key block k0 .. k0 + 63.  The
+// K fragments come from global memory (L2) as in hdattn_fwd_kernel; nothing is staged in LDS and the kernels have no barrier.  An
+// output element depends on its own query row and key rows alone, so a row's outputs are the same bits wherever the row lands in a
+// tile: however the rows are cut into calls (row0 / nrows), however the batch is cut, packed or split operands.
+//
+// BOTH score kernels make passes over the key blocks, K re-read from L2, instead of rescaling running sums (the issue's other
+// choice): the row maximum is then exact and the sums are taken against the final maximum only.
+//   pass 1   m = max_j s_j.  Per lane over its keys (padded keys count as -inf), then fmaxf with lane ^ 16 and lane ^ 32.  A maximum
+//            does not depend on the order: smax = m is the largest scaled logit bit for bit.
+//   pass 2   e_j = __expf(s_j - m) for the lane's keys j < Lk, in the order key block, kt, r; per lane, each starting from 0.f:
+//              l  += e_j                 es += e_j * s_j
+//              ep += e_j  if j < n_prefix              ed += e_j * dist(i, j)  if j >= n_prefix and i >= n_prefix
+//            (hipcc may contract each product and sum into one fma: the envelope charges the sum, which covers both).  Then the four
+//            lanes of a query meet once, in a fixed butterfly:  x += x(lane ^ 16);  x += x(lane ^ 32)  for l, es, ep, ed.
+//   dist(i, j) = v_sqrt_f32((float)(dy * dy + dx * dx)) with dy, dx the integer row / column differences of the grid positions
+//            ((t - n_prefix) / gw, (t - n_prefix) % gw); the argument is an exact integer below 2^24, the instruction is within 1 ulp.
+//   vtx_attn_map_stats stores, per query row i (fp32 [B, nH, Lq, 5]):
+//              lse = m + __logf(l)       entropy = lse - es / l       smax = m       prefix = ep / l       dist = ed / l
+//            (IEEE divisions).  dist is 0.f for a prefix query row and with gh = gw = 0.
+//   vtx_attn_map_rows runs passes 1 and 2 for l alone -- the same lanes, the same order, hence the same bits of m, l and lse as
+//            vtx_attn_map_stats -- and a third pass that stores p_j = __expf(s_j - m) / l (IEEE division) and lse = m + __logf(l).
+// P is never written by vtx_attn_map_stats and no buffer of Lq * Lk exists per problem.
+//
+// vtx_attn_map_meter: one workgroup adds a stats tensor to the fp64 meter [n_layer, nH, 6] in a fixed order (as knn_meter_kernel):
+// thread t sums the rows t, t + 256, ... of head h (row = image * Lq + query) in fp64, a halving tree in LDS joins the threads.
+//
+// vtx_attn_mass_mask: the thresholding of DINO's visualize_attention (sort ascending, cumulative sum, keep what lies above 1 - keep
+// of the mass), with these rules.  Values below zero and NaNs count as 0.f.  One workgroup per map sorts the (value, index) pairs
+// ascending -- equal values: the lower index first -- by a bitonic network in LDS (4096 pairs of 8 bytes = 32 KB).  THE RUNNING SUM,
+// in fp32, in that order, is formed in chunks of 16 consecutive sorted elements, whatever n and the launch geometry:
+//     w[c][0] = v[16 c],  w[c][i] = w[c][i - 1] + v[16 c + i]      inside chunk c, left to right
+//     P[0] = 0.f,  P[c] = (..((0.f + w[0][15]) + w[1][15]) + ..) + w[c - 1][15]      over the full chunks in front of c, left to right
+//     run[16 c + i] = P[c] + w[c][i];     total = run[n - 1];     thr = (1.f - keep) * total   (fp32 subtraction, fp32 product)
+// Element e is kept (byte 1) iff run[its sorted position] > thr, else byte 0.  A sum that hits thr exactly is not kept; an all-zero
+// map keeps nothing.  DINO's script divides the values by their total before the running sum and compares with 1 - keep; this
+// kernel does not divide (one rounding per element less, and an all-zero map has no 0 / 0): the only difference.
+//
+// No floating-point atomics anywhere; every sum has a fixed order, so the same inputs give the same bits.
+//
+// Budget (hipcc resource remarks, gfx950, no scratch in any instantiation): DESIGN.md section 7i.
+#include "vtx_common.h"
+
+#define AM_KB 64                 // keys per block (4 tiles of 16)
+#define AM_MASK_MAX 4096         // elements of a map at most
+#define AM_CHUNK 16              // elements of a chunk of the running sum
+
+struct AmGeom {
+  int Lq, Lk, nH, D;
+  int qblocks;                   // ceil(nrows / 64)
+  int row0, nrows;               // query rows row0 .. row0 + nrows - 1 (stats: 0, Lq)
+  int n_prefix, gh, gw;          // stats only; gw == 0: dist off
+  int64_t ldq, ldkv;
+  float scale;
+};
+
+template <typename T> __device__ __forceinline__ Vec8<T> am_load(const T* head, int d0, int D, bool valid) {
+  const bool in = d0 < D;
+  return load8_clamped<T>(head + (in ? d0 : 0), valid && in);
+}
+
+// The scaled scores of key block k0 against the wave's query fragments: st[kt][r] = s(query c, key k0 + 16 kt + 4 g + r); keys >= Lk are
+// -inf.  The chain of hdattn_fwd_kernel, read in the block of its MFMAs (acc_settle).
+template <typename T, int DS>
+__device__ __forceinline__ void am_scores(f32x4 (&st)[4], const Vec8<T> (&qf)[DS], const T* __restrict__ kb, int64_t krow0, int64_t ld,
+                                          int k0, int Lk, int D, float scale, int c_, int g_) {
+#pragma unroll
+  for (int kt = 0; kt < 4; ++kt) {
+    st[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int key = k0 + kt * 16 + c_;
+    const bool kv = key < Lk;
+    const T* kp = kb + (krow0 + (kv ? key : 0)) * ld;
+#pragma unroll
+    for (int ds = 0; ds < DS; ++ds) mma16(am_load<T>(kp, ds * 32 + g_ * 8, D, kv), qf[ds], st[kt]);   // S^T[key][q = c_]
+    acc_settle(st[kt]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int kk = k0 + kt * 16 + g_ * 4 + r;
+      st[kt][r] = kk < Lk ? st[kt][r] * scale : -INFINITY;
+    }
+    acc_settle(st[kt]);          // the rounded product IS the score: no use of it may be contracted into an fma of acc and scale
+  }
+}
+
+// What every score kernel starts with: the wave's query (row0 + 16 * (4 block + wave) + c), its fragments, pass 1 and pass 2 for l.
+template <typename T, int DS> struct AmRow {
+  Vec8<T> qf[DS];
+  const T* kb;
+  int64_t krow0;
+  int bh, qi, q, c_, g_;         // qi: index inside the call's rows; q = row0 + qi
+  bool qv;
+  float m;
+
+  __device__ __forceinline__ void init(const T* __restrict__ qp, const T* __restrict__ kp, const AmGeom& g) {
+    bh = blockIdx.x / g.qblocks;
+    const int qblk = blockIdx.x - bh * g.qblocks;
+    const int b = bh / g.nH, h = bh - b * g.nH;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    c_ = lane & 15; g_ = lane >> 4;
+    qi = (qblk * 4 + wave) * 16 + c_;
+    qv = qi < g.nrows;
+    q = g.row0 + (qv ? qi : 0);
+    const T* qb = qp + h * g.D + ((int64_t)b * g.Lq + q) * g.ldq;
+#pragma unroll
+    for (int ds = 0; ds < DS; ++ds) qf[ds] = am_load<T>(qb, ds * 32 + g_ * 8, g.D, qv);
+    kb = kp + h * g.D;
+    krow0 = (int64_t)b * g.Lk;
+  }
+  __device__ __forceinline__ bool wave_idle(const AmGeom& g) const { return qi - c_ >= g.nrows; }   // wave-uniform; no barrier follows
+  __device__ __forceinline__ void scores(f32x4 (&st)[4], int k0, const AmGeom& g) const {
+    am_scores<T, DS>(st, qf, kb, krow0, g.ldkv, k0, g.Lk, g.D, g.scale, c_, g_);
+  }
+  __device__ __forceinline__ void pass_max(const AmGeom& g) {
+    float mb = -INFINITY;
+    for (int k0 = 0; k0 < g.Lk; k0 += AM_KB) {
+      f32x4 st[4];
+      scores(st, k0, g);
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mb = fmaxf(mb, st[kt][r]);
+    }
+    mb = fmaxf(mb, shfl_xor_f(mb, 16));
+    m = fmaxf(mb, shfl_xor_f(mb, 32));
+  }
+};
+__device__ __forceinline__ float am_join(float x) {          // the butterfly of a query's four lanes
+  x += shfl_xor_f(x, 16);
+  x += shfl_xor_f(x, 32);
+  return x;
+}
+
+// ------------------------------------------------------------------------------------------------- rows of P
+// grid = B * nH * ceil(nrows / 64) workgroups of 4 waves; p [B, nH, nrows, Lk], lse [B, nH, nrows]
+template <typename T, int DP>
+__global__ __launch_bounds__(256) void attn_map_rows_kernel(const T* __restrict__ qp, const T* __restrict__ kp, float* __restrict__ p,
+                                                           float* __restrict__ lse, AmGeom g) {
+  constexpr int DS = DP / 32;
+  AmRow<T, DS> row;
+  row.init(qp, kp, g);
+  if (row.wave_idle(g)) return;
+  row.pass_max(g);
+  const float m = row.m;
+  float l = 0.f;
+  for (int k0 = 0; k0 < g.Lk; k0 += AM_KB) {
+    f32x4 st[4];
+    row.scores(st, k0, g);
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (k0 + kt * 16 + row.g_ * 4 + r < g.Lk) l += __expf(st[kt][r] - m);
+  }
+  l = am_join(l);
+  const int64_t orow = (int64_t)row.bh * g.nrows + row.qi;
+  if (row.qv && row.g_ == 0) lse[orow] = m + __logf(l);
+  for (int k0 = 0; k0 < g.Lk; k0 += AM_KB) {
+    f32x4 st[4];
+    row.scores(st, k0, g);
+    if (row.qv) {
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int kk = k0 + kt * 16 + row.g_ * 4 + r;
+          if (kk < g.Lk) p[orow * g.Lk + kk] = __expf(st[kt][r] - m) / l;
+        }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------- statistics
+// grid = B * nH * ceil(Lq / 64); stats [B, nH, Lq, 5] = lse, entropy, smax, prefix, dist
+template <typename T, int DP>
+__global__ __launch_bounds__(256) void attn_map_stats_kernel(const T* __restrict__ qp, const T* __restrict__ kp, float* __restrict__ stats,
+                                                            AmGeom g) {
+  constexpr int DS = DP / 32;
+  AmRow<T, DS> row;
+  row.init(qp, kp, g);
+  if (row.wave_idle(g)) return;
+  row.pass_max(g);
+  const float m = row.m;
+  const int np = g.n_prefix, gw = g.gw;
+  const bool on_grid = gw > 0 && row.q >= np;                       // this query has a grid position and dist is on
+  int qy = 0, qx = 0;
+  if (on_grid) { qy = (row.q - np) / gw; qx = (row.q - np) - qy * gw; }
+  float l = 0.f, es = 0.f, ep = 0.f, ed = 0.f;
+  for (int k0 = 0; k0 < g.Lk; k0 += AM_KB) {
+    f32x4 st[4];
+    row.scores(st, k0, g);
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+      const int kb0 = k0 + kt * 16 + row.g_ * 4;
+      // grid position of the first patch key of the lane's four: key max(kb0, n_prefix); the next ones step along the row
+      const int ts = kb0 > np ? kb0 - np : 0;
+      int ky = 0, kx = ts;
+      if (on_grid) { ky = ts / gw; kx = ts - ky * gw; }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int kk = kb0 + r;
+        if (kk < g.Lk) {
+          const float s = st[kt][r];
+          const float e = __expf(s - m);
+          l += e;
+          es += e * s;
+          if (kk < np) {
+            ep += e;
+          } else if (on_grid) {
+            const int dy = ky - qy, dx = kx - qx;
+            ed += e * __builtin_amdgcn_sqrtf((float)(dy * dy + dx * dx));
+            if (++kx == gw) { kx = 0; ++ky; }
+          }
+        }
+      }
+    }
+  }
+  l = am_join(l);
+  es = am_join(es);
+  ep = am_join(ep);
+  ed = am_join(ed);
+  if (row.qv && row.g_ == 0) {
+    const float ls = m + __logf(l);
+    float* out = stats + ((int64_t)row.bh * g.Lq + row.q) * 5;
+    out[0] = ls;
+    out[1] = ls - es / l;
+    out[2] = m;
+    out[3] = ep / l;
+    out[4] = on_grid ? ed / l : 0.f;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------- meter
+// meter[layer][h] = [queries, sum entropy, sum prefix, sum dist over patch queries, patch queries, max smax]
+__global__ __launch_bounds__(256) void attn_map_meter_kernel(const float* __restrict__ stats, double* __restrict__ meter, int layer, int B,
+                                                            int nH, int Lq, int n_prefix) {
+  __shared__ double red[4][256];
+  const int tid = threadIdx.x;
+  const int64_t rows = (int64_t)B * Lq;
+  for (int h = 0; h < nH; ++h) {
+    double se = 0.0, sp = 0.0, sd = 0.0, mx = -INFINITY;
+    for (int64_t i = tid; i < rows; i += 256) {
+      const int64_t b = i / Lq;
+      const int q = (int)(i - b * Lq);
+      const float* s = stats + ((b * nH + h) * Lq + q) * 5;
+      se += (double)s[1];
+      sp += (double)s[3];
+      if (q >= n_prefix) sd += (double)s[4];
+      mx = fmax(mx, (double)s[2]);
+    }
+    red[0][tid] = se; red[1][tid] = sp; red[2][tid] = sd; red[3][tid] = mx;
+    __syncthreads();
+    for (int sft = 128; sft >= 1; sft >>= 1) {
+      if (tid < sft) {
+        red[0][tid] += red[0][tid + sft]; red[1][tid] += red[1][tid + sft]; red[2][tid] += red[2][tid + sft];
+        red[3][tid] = fmax(red[3][tid], red[3][tid + sft]);
+      }
+      __syncthreads();
+    }
+    if (tid == 0) {
+      double* o = meter + ((int64_t)layer * nH + h) * 6;
+      o[0] += (double)rows; o[1] += red[0][0]; o[2] += red[1][0]; o[3] += red[2][0];
+      o[4] += (double)B * (double)(Lq - n_prefix);
+      o[5] = fmax(o[5], red[3][0]);
+    }
+    __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------------------------------------- mass mask
+// one workgroup per map; n2 = the power of two >= max(n, 2)
+__global__ __launch_bounds__(256) void attn_mass_mask_kernel(const float* __restrict__ maps, uint8_t* __restrict__ mask, int n, int n2,
+                                                            float keep) {
+  __shared__ unsigned long long srt[AM_MASK_MAX];             // (value bits << 32) | index: non-negative floats order as their bits
+  __shared__ float tot[AM_MASK_MAX / AM_CHUNK];
+  __shared__ float total_s;
+  const int tid = threadIdx.x;
+  const float* src = maps + (int64_t)blockIdx.x * n;
+  uint8_t* dst = mask + (int64_t)blockIdx.x * n;
+  for (int i = tid; i < n2; i += 256) {
+    unsigned long long kv = ~0ull;                             // the pad sorts behind every element
+    if (i < n) kv = ((unsigned long long)__float_as_uint(fmaxf(src[i], 0.f)) << 32) | (unsigned)i;   // below zero, NaN, -0.f: +0.f
+    srt[i] = kv;
+  }
+  __syncthreads();
+  for (int size = 2; size <= n2; size <<= 1)
+    for (int stride = size >> 1; stride >= 1; stride >>= 1) {
+      for (int t = tid; t < (n2 >> 1); t += 256) {
+        const int lo = ((t / stride) * stride << 1) + (t % stride), hi = lo + stride;
+        const bool up = (lo & size) == 0;
+        const unsigned long long a = srt[lo], b = srt[hi];
+        if ((a > b) == up) { srt[lo] = b; srt[hi] = a; }
+      }
+      __syncthreads();
+    }
+  // chunk c of 16 sorted elements belongs to thread c (n <= 4096 = 256 * 16)
+  const int e0 = tid * AM_CHUNK;
+  float w[AM_CHUNK];
+  float acc = 0.f;
+#pragma unroll
+  for (int i = 0; i < AM_CHUNK; ++i) {
+    const float v = e0 + i < n ? __uint_as_float((unsigned)(srt[e0 + i] >> 32)) : 0.f;
+    acc = i == 0 ? v : acc + v;
+    w[i] = acc;
+  }
+  tot[tid] = acc;
+  __syncthreads();
+  float P = 0.f;
+  for (int c = 0; c < tid && c * AM_CHUNK < n; ++c) P += tot[c];
+#pragma unroll
+  for (int i = 0; i < AM_CHUNK; ++i) w[i] = P + w[i];
+  if (e0 <= n - 1 && n - 1 < e0 + AM_CHUNK) {
+    float last = w[0];
+#pragma unroll
+    for (int i = 1; i < AM_CHUNK; ++i)
+      if (e0 + i == n - 1) last = w[i];
+    total_s = last;
+  }
+  __syncthreads();
+  const float thr = (1.f - keep) * total_s;
+#pragma unroll
+  for (int i = 0; i < AM_CHUNK; ++i)
+    if (e0 + i < n) dst[(unsigned)(srt[e0 + i] & 0xffffffffull)] = w[i] > thr ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------------------- host
+template <typename T, int DP> static int am_rows_t(const void* q, const void* k, float* p, float* lse, int B, const AmGeom& g, hipStream_t st) {
+  hipLaunchKernelGGL((attn_map_rows_kernel<T, DP>), dim3((unsigned)(B * g.nH * g.qblocks)), dim3(256), 0, st, (const T*)q, (const T*)k, p,
+                     lse, g);
+  return vtx_check_launch();
+}
+template <typename T, int DP> static int am_stats_t(const void* q, const void* k, float* stats, int B, const AmGeom& g, hipStream_t st) {
+  hipLaunchKernelGGL((attn_map_stats_kernel<T, DP>), dim3((unsigned)(B * g.nH * g.qblocks)), dim3(256), 0, st, (const T*)q, (const T*)k,
+                     stats, g);
+  return vtx_check_launch();
+}
+#define AM_DISPATCH_T(FN, T, ...)                                                                     \
+  (D <= 32 ? FN<T, 32>(__VA_ARGS__) : D <= 64 ? FN<T, 64>(__VA_ARGS__) : D <= 96 ? FN<T, 96>(__VA_ARGS__) : FN<T, 128>(__VA_ARGS__))
+#define AM_DISPATCH(FN, ...) (dtype == VTX_BF16 ? AM_DISPATCH_T(FN, bf16, __VA_ARGS__) : AM_DISPATCH_T(FN, float, __VA_ARGS__))
+
+// Everything the two score entries refuse, before any launch, with the codes of the vtx_attn_hd_* entries.
+static int am_geom(AmGeom& g, int B, int Lq, int Lk, int nH, int D, int row0, int nrows, int dtype, int64_t ldq, int64_t ldkv) {
+  if (dtype != VTX_BF16 && dtype != VTX_F32) return VTX_ERR_DTYPE;
+  if (B <= 0 || Lq <= 0 || Lk <= 0 || nH <= 0 || D < 8 || D > 128 || D % 8 != 0) return VTX_ERR_SHAPE;
+  if ((int64_t)B * Lq >= 0x7fffffffLL || (int64_t)B * Lk >= 0x7fffffffLL || (int64_t)nH * D >= 0x7fffffffLL) return VTX_ERR_SHAPE;
+  if (row0 < 0 || nrows <= 0 || (int64_t)row0 + nrows > Lq) return VTX_ERR_SHAPE;
+  const int64_t hd = (int64_t)nH * D;
+  if (ldq < hd || ldkv < hd) return VTX_ERR_SHAPE;
+  if (ldq % 8 || ldkv % 8) return VTX_ERR_ALIGN;
+  const int qblocks = (nrows + AM_KB - 1) / AM_KB;
+  if ((int64_t)B * nH * qblocks >= 0x7fffffffLL) return VTX_ERR_SHAPE;
+  g = AmGeom{Lq, Lk, nH, D, qblocks, row0, nrows, 0, 0, 0, ldq, ldkv, 1.0f / sqrtf((float)D)};
+  return VTX_OK;
+}
+static bool am_aligned(const void* p, uintptr_t mask) { return ((uintptr_t)p & mask) == 0; }
+
+extern "C" {
+
+/* include/vtx.h: vtx_attn_map_rows */
+int vtx_attn_map_rows(const void* q, const void* k, int64_t ldq, int64_t ldkv, float* p, float* lse, int B, int Lq, int Lk, int nH, int D,
+                      int row0, int nrows, int dtype, void* stream) {
+  if (!q || !k || !p || !lse) return VTX_ERR_NULL;
+  AmGeom g;
+  int rc = am_geom(g, B, Lq, Lk, nH, D, row0, nrows, dtype, ldq, ldkv);
+  if (rc) return rc;
+  if (!am_aligned(q, 15) || !am_aligned(k, 15) || !am_aligned(p, 3) || !am_aligned(lse, 3)) return VTX_ERR_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  return AM_DISPATCH(am_rows_t, q, k, p, lse, B, g, st);
+}
+
+/* include/vtx.h: vtx_attn_map_stats */
+int vtx_attn_map_stats(const void* q, const void* k, int64_t ldq, int64_t ldkv, float* stats, int B, int Lq, int Lk, int nH, int D,
+                       int n_prefix, int gh, int gw, int dtype, void* stream) {
+  if (!q || !k || !stats) return VTX_ERR_NULL;
+  AmGeom g;
+  int rc = am_geom(g, B, Lq, Lk, nH, D, 0, Lq > 0 ? Lq : 1, dtype, ldq, ldkv);
+  if (rc) return rc;
+  if (n_prefix < 0 || n_prefix > (Lq < Lk ? Lq : Lk)) return VTX_ERR_SHAPE;
+  if (gh != 0 || gw != 0) {          // keys and queries share one grid
+    if (gh <= 0 || gw <= 0 || (int64_t)gh * gw != (int64_t)Lk - n_prefix || (int64_t)gh * gw != (int64_t)Lq - n_prefix) return VTX_ERR_SHAPE;
+  }
+  if (!am_aligned(q, 15) || !am_aligned(k, 15) || !am_aligned(stats, 3)) return VTX_ERR_ALIGN;
+  g.n_prefix = n_prefix; g.gh = gh; g.gw = gw;
+  hipStream_t st = (hipStream_t)stream;
+  return AM_DISPATCH(am_stats_t, q, k, stats, B, g, st);
+}
+
+/* include/vtx.h: vtx_attn_map_meter */
+int vtx_attn_map_meter(const float* stats, double* meter, int layer, int B, int nH, int Lq, int n_prefix, void* stream) {
+  if (!stats || !meter) return VTX_ERR_NULL;
+  if (layer < 0 || B <= 0 || nH <= 0 || Lq <= 0 || n_prefix < 0 || n_prefix > Lq) return VTX_ERR_SHAPE;
+  if ((int64_t)B * Lq >= 0x7fffffffLL || (int64_t)layer * nH >= 0x7fffffffLL) return VTX_ERR_SHAPE;
+  if (!am_aligned(stats, 3) || !am_aligned(meter, 7)) return VTX_ERR_ALIGN;
+  hipLaunchKernelGGL(attn_map_meter_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, stats, meter, layer, B, nH, Lq, n_prefix);
+  return vtx_check_launch();
+}
+
+/* include/vtx.h: vtx_attn_mass_mask */
+int vtx_attn_mass_mask(const float* maps, uint8_t* mask, int n_maps, int n, float keep, void* stream) {
+  if (!maps || !mask) return VTX_ERR_NULL;
+  if (n_maps <= 0 || n <= 0 || n > AM_MASK_MAX) return VTX_ERR_SHAPE;
+  if (!(keep > 0.f) || !(keep <= 1.f)) return VTX_ERR_SHAPE;
+  if (!am_aligned(maps, 3)) return VTX_ERR_ALIGN;
+  int n2 = 2;
+  while (n2 < n) n2 <<= 1;
+  hipLaunchKernelGGL(attn_mass_mask_kernel, dim3((unsigned)n_maps), dim3(256), 0, (hipStream_t)stream, maps, mask, n, n2, keep);
+  return vtx_check_launch();
+}
+
+}  // extern "C"

@@ -143,6 +143,48 @@ class VisionTransformer(nn.Module):
         # reference: norm(out)[:, 0]; LayerNorm is per token, so normalising only the cls rows is identical
         return self.norm(tokens[:, 0])
 
+    def attention_inputs(self, input, layers=(-1,)):
+        """The QKV projections that enter the attention of ``layers`` (indices into ``self.layers``, negative from the end), for
+        ``vtx.attnmap``: what a forward hook on the reference's ``attn`` (vit.py:36-39) is computed from.  Needs ``eval()``,
+        ``torch.no_grad()`` and ONE image tensor on the device (a list of crops is refused).  The forward is forward_feature's
+        own, piece by piece and untouched; in front of each requested layer its LayerNorm and QKV linear run once more as
+        separate launches (the fused layer call keeps its projection to itself): one extra LayerNorm + QKV GEMM per tapped layer.
+        -> ({layer index: qkv (B, L, 3 dim)}, the CLS feature forward_feature returns, the patch grid (gh, gw))."""
+        from vtx.ops import VtxError
+        if isinstance(input, (list, tuple)) or not torch.is_tensor(input) or input.dim() != 4:
+            raise VtxError("vtx: attention_inputs takes one (B, 3, H, W) image tensor, not a list of crops")
+        if self.training:
+            raise VtxError("vtx: attention_inputs needs model.eval(): attention under dropout / DropPath is not inspected")
+        if torch.is_grad_enabled():
+            raise VtxError("vtx: attention_inputs runs under torch.no_grad(): none of its outputs has a gradient")
+        depth = len(self.layers)
+        want = set()
+        for l in layers:
+            if not -depth <= int(l) < depth:
+                raise VtxError(f"vtx: attention_inputs: layer {l} of a model of {depth} layers")
+            want.add(int(l) % depth)
+        if not input.is_cuda:
+            raise VtxError("vtx: attention_inputs needs device tensors (there is no CPU fallback)")
+        patch = self.patch_embedding.linear.kernel_size
+        grid = (input.shape[2] // patch[0], input.shape[3] // patch[1])
+        taps = {}
+        with VF.weight_scope(self, input):
+            tokens = self.patch_embedding(input)
+            tokens = VF.VitAssembleFn.apply(tokens, self.cls_token, resize_position_grid(self.pos_embed, tokens.shape[1]))
+            tokens = self.pos_drop(tokens)
+            with drop_path_scope(self, tokens.shape[0], tokens.device):
+                for i, layer in enumerate(self.layers):
+                    if i in want:
+                        normed = layer.norm_attn(tokens)
+                        taps[i] = VF.LinearFn.apply(normed.to(VF.compute_dtype(normed)), layer.attn.qkv.weight, layer.attn.qkv.bias)
+                    tokens = layer(tokens)
+            return taps, self.norm(tokens[:, 0]), grid
+
+    def attention_maps(self, input, layer=-1):
+        """DINO's CLS self-attention maps of ``layer`` as (B, heads, gh, gw) float32: vtx.attnmap.cls_attention_maps."""
+        from vtx.attnmap import cls_attention_maps
+        return cls_attention_maps(self, input, layer)
+
     def interpolate_pos_embedding(self, input, pos_embed):
         """Reference call style (vit.py:153-175): ``input`` is the (batch, 1 + n_patch, dim) token tensor."""
         return resize_position_grid(pos_embed, input.shape[1] - 1)

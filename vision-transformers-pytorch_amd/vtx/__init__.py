@@ -13,11 +13,16 @@
                   vtx.FeatureBank, ...)
   vtx.probe       linear-probe evaluation of frozen features: LinearProbe (many heads trained at once, fused linear +
                   cross-entropy kernels), ProbeMeter, linear_probe_evaluate (also reachable as vtx.LinearProbe, ...)
+  vtx.attnmap     attention maps and per-head attention statistics without writing P: attention_rows, attention_stats,
+                  mass_mask, cls_attention_maps, AttentionStatsMeter, attention_statistics (also reachable as
+                  vtx.attention_rows, ...)
 """
 
 _KNN_NAMES = ("FeatureBank", "KnnMeter", "knn_search", "extract_features", "knn_evaluate", "ShardedFeatureBank",
               "knn_search_sharded")
 _PROBE_NAMES = ("LinearProbe", "ProbeMeter", "linear_probe_evaluate")
+_ATTNMAP_NAMES = ("attention_rows", "attention_stats", "mass_mask", "cls_attention_maps", "AttentionStatsMeter",
+                  "attention_statistics")
 
 
 def __getattr__(name):
@@ -32,4 +37,7 @@ def __getattr__(name):
     if name in _PROBE_NAMES:
         from . import probe
         return getattr(probe, name)
+    if name in _ATTNMAP_NAMES:
+        from . import attnmap
+        return getattr(attnmap, name)
     raise AttributeError(f"module 'vtx' has no attribute {name!r}")

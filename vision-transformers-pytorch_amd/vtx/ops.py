@@ -1581,6 +1581,77 @@ def knn_vote(val, idx, bank_labels, query_labels, ks, n_class, T, meter=None):
     return rank, pred
 
 
+# ------------------------------------------------------------------------------- attention maps (csrc/attention_maps.hip)
+def _attn_map_operands(q, k, n_head, what):
+    """(B, Lq, Lk, D, ldq, ldkv) of a query view (B, Lq, >= nH D) and a key view (B, Lk, >= nH D) whose first nH * D columns are
+    the heads: a unit last stride and one row stride over all B * L rows, so that pointer and stride describe it -- a view of
+    the packed projection or of the kv pair goes in as it is, nothing is copied."""
+    for t in (q, k):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise VtxError(f"vtx: {what} needs device tensors (there is no CPU fallback)")
+        if t.dim() != 3 or t.numel() == 0 or t.stride(2) != 1 or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1)):
+            raise VtxError(f"vtx: {what} takes (B, L, C) views with a unit last stride and one row stride, got {tuple(t.shape)} "
+                           f"strides {t.stride()}")
+    n_head = int(n_head)
+    if q.dtype != k.dtype or q.shape[0] != k.shape[0] or n_head < 1 or q.shape[2] % n_head or k.shape[2] != q.shape[2]:
+        raise VtxError(f"vtx: {what}: q {tuple(q.shape)} {q.dtype} and k {tuple(k.shape)} {k.dtype} for {n_head} heads")
+    # (the stride of a dimension of extent 1 says nothing: a lone row per image is addressed by the image stride)
+    ld = lambda t: t.stride(1) if t.shape[1] > 1 else (t.stride(0) if t.shape[0] > 1 else t.shape[2])
+    return q.shape[0], q.shape[1], k.shape[1], q.shape[2] // n_head, ld(q), ld(k)
+
+
+def attn_map_rows(q, k, n_head, row0=0, nrows=1):
+    """Rows row0 .. row0 + nrows - 1 of softmax(q k^T / sqrt(D)) for every image and head.  ``q`` (B, Lq, nH D) and ``k``
+    (B, Lk, nH D) are views (see _attn_map_operands).  -> (p fp32 [B, nH, nrows, Lk], lse fp32 [B, nH, nrows]); rules and
+    refusals: include/vtx.h."""
+    B, Lq, Lk, D, ldq, ldkv = _attn_map_operands(q, k, n_head, "attn_map_rows")
+    row0, nrows = int(row0), int(nrows)
+    if row0 < 0 or nrows < 1 or row0 + nrows > Lq:
+        raise VtxError(f"vtx: attn_map_rows: rows {row0}..{row0 + nrows} of {Lq}")
+    p = torch.empty((B, int(n_head), nrows, Lk), dtype=torch.float32, device=q.device)
+    lse = torch.empty((B, int(n_head), nrows), dtype=torch.float32, device=q.device)
+    check(_lib.load().vtx_attn_map_rows(_p(q), _p(k), ldq, ldkv, _p(p), _p(lse), B, Lq, Lk, int(n_head), D, row0, nrows, _dt(q),
+                                        _stream()), "vtx_attn_map_rows")
+    return p, lse
+
+
+def attn_map_stats(q, k, n_head, n_prefix=1, grid=None):
+    """Per-query attention statistics [lse, entropy, smax, prefix mass, mean distance] without writing P.  ``grid`` = (gh, gw)
+    of the patch tokens behind the ``n_prefix`` prefix tokens, shared by queries and keys, or None: the distance is then 0.
+    -> stats fp32 [B, nH, Lq, 5]; rules and refusals: include/vtx.h."""
+    B, Lq, Lk, D, ldq, ldkv = _attn_map_operands(q, k, n_head, "attn_map_stats")
+    gh, gw = (0, 0) if grid is None else (int(grid[0]), int(grid[1]))
+    stats = torch.empty((B, int(n_head), Lq, 5), dtype=torch.float32, device=q.device)
+    check(_lib.load().vtx_attn_map_stats(_p(q), _p(k), ldq, ldkv, _p(stats), B, Lq, Lk, int(n_head), D, int(n_prefix), gh, gw,
+                                         _dt(q), _stream()), "vtx_attn_map_stats")
+    return stats
+
+
+def attn_map_meter(stats, meter, layer, n_prefix=1):
+    """Add ``stats`` fp32 [B, nH, Lq, 5] to ``meter`` float64 [n_layer, nH, 6] at ``layer`` (include/vtx.h has the six values)."""
+    _dev(stats, meter)
+    if stats.dim() != 4 or stats.shape[3] != 5 or stats.dtype != torch.float32:
+        raise VtxError("vtx: attn_map_meter takes the float32 [B, nH, Lq, 5] tensor of attn_map_stats")
+    B, nH, Lq, _ = stats.shape
+    if meter.dtype != torch.float64 or meter.dim() != 3 or meter.shape[1] != nH or meter.shape[2] != 6:
+        raise VtxError(f"vtx: the attention meter is a float64 device tensor [n_layer, {nH}, 6]")
+    if not 0 <= int(layer) < meter.shape[0]:
+        raise VtxError(f"vtx: attn_map_meter: layer {layer} of a meter of {meter.shape[0]} layers")
+    check(_lib.load().vtx_attn_map_meter(_p(stats), _p(meter), int(layer), B, nH, Lq, int(n_prefix), _stream()), "vtx_attn_map_meter")
+
+
+def attn_mass_mask(maps, keep=0.6):
+    """uint8 mask of ``maps``' shape: per map (the last dimension, n <= 4096 non-negative fp32 values) the elements that hold
+    the upper ``keep`` of the mass, by the sort and running sum include/vtx.h documents."""
+    _dev(maps)
+    if maps.dtype != torch.float32 or maps.dim() < 1:
+        raise VtxError("vtx: attn_mass_mask takes float32 maps")
+    n = maps.shape[-1]
+    mask = torch.empty(maps.shape, dtype=torch.uint8, device=maps.device)
+    check(_lib.load().vtx_attn_mass_mask(_p(maps), _p(mask), maps.numel() // n, n, float(keep), _stream()), "vtx_attn_mass_mask")
+    return mask
+
+
 # ------------------------------------------------------------------------------- data movement
 def cast_desc_bytes():
     return _lib.load().vtx_cast_desc_bytes()
