@@ -46,8 +46,9 @@ extern "C" {
 const char* vtx_strerror(int code);
 /* ABI version of the library (bumped on any signature change). */
 int vtx_abi_version(void);
-/* Compute units of the current device (256 on MI355X): what the one-workgroup-per-CU kernels size their grids and the
- * dispatch heuristics their thresholds with; the Python mirrors of those heuristics (vtx/ops.py) ask here. */
+/* Compute units of the current device (256 on MI355X; 256 when no device can be asked): what the one-workgroup-per-CU kernels size their
+ * grids and the dispatch heuristics their thresholds with.  The heuristics themselves live in the library only: the bindings ask
+ * vtx_gemm_route / vtx_wgrad_route / vtx_wattn_route (below) which kernel a launch takes. */
 int vtx_cu_count(void);
 /* Test helper: fill the LDS of every CU with `pattern` (160-KB workgroups, `rounds` per CU): LDS is not cleared between workgroups, and a
  * kernel that reads LDS it never wrote sees what the previous workgroup left there (tests/test_gpu_lds_poison.py). */
@@ -115,6 +116,42 @@ int vtx_layernorm_bwd(const void* dy, const void* x, const float* mean, const fl
 int vtx_gemm(int mode, int dtype, const void* A, const void* B, void* C, int M, int N, int K, int64_t lda,
              int64_t ldb, int64_t ldc, const float* bias, const void* resid, const float* rowscale,
              int rows_per_scale, void* aux_out, const void* aux_in, int act, void* stream);
+/* ---- Routing queries.  Which kernel instantiation a GEMM, a weight gradient or a window-attention launch takes is decided once, in the
+ * library (csrc/gemm.hip gemm_route and its per-family parts, wgrad_group_route, wattn_route), from the shapes, the operands that are
+ * present, the dispatch switches and the CU count.  The launchers switch on that decision; these entries return the same decision for a
+ * launch described by shape alone, with the name of the instantiation as rocprofv3 prints it (abbreviated as bench.py and the tests know
+ * it).  They touch no device memory, launch nothing and work without a GPU.  VtxRoute / VtxGemmQuery: vtx_layer_desc_bytes(4 / 5). */
+typedef struct VtxRoute {
+  int family;                 /* GEMM: 1 skinny | 2 two-group | 3 A-stationary | 4 LDS-DMA wave-private epilogue | 5 LDS-DMA | 6 register-staged;
+                                 weight gradient: 1 LDS-DMA 128 x 128 | 2 wide | 3 register-staged;  window attention: 1 one wave | 2 four waves */
+  int tile_m, tile_n, tile_k, stages, waves;   /* tiled families: tile, k-depth, ring stages; waves along N (LDS-DMA) / per workgroup */
+  int wmf, nf, ktiles;        /* two-group: tile height / 32 and tile width / 64; k-tiles of skinny (K / 32) and A-stationary (K / 64) */
+  int mapped, act, resid, aux;   /* what the instantiation is specialised on (where its family templates on it) */
+  int wide_j, tiles;          /* wide weight gradient: tile width / 64 and the tiles of the group */
+  int reserved;
+  char label[96];
+} VtxRoute;
+#define VTX_Q_RESID 1         /* (bits 0..3 = the flag bits of a VtxTimerRec) */
+#define VTX_Q_AUXOUT 2
+#define VTX_Q_AUXIN 4
+#define VTX_Q_MAPPED 8
+#define VTX_Q_BIAS 16
+#define VTX_Q_ROWSCALE 32
+#define VTX_Q_INPLACE 64      /* resid == C */
+typedef struct VtxGemmQuery {
+  int mode, dtype, M, N, K, act;   /* as vtx_gemm; mode 2: the register-staged weight gradient dW[M, N] over K tokens */
+  int flags;                  /* VTX_Q_*: the operands that are present (contiguous leading dimensions assumed) */
+  int Mk, map_T;              /* VTX_Q_MAPPED: rows computed and rows per sample; map_T == 0: unknown (a timer record) -- one sample of Mk rows */
+  int rows_per_scale;         /* with VTX_Q_ROWSCALE (<= 0: 1; a mapped launch: map_T) */
+} VtxGemmQuery;
+int vtx_gemm_route(const VtxGemmQuery* q, VtxRoute* out);
+/* nprob == 1 and flags bit 0 clear: vtx_wgrad (flags bit 1: a rowscale is present);  flags bit 0: the grouped launch (bit 2: row-mapped) */
+int vtx_wgrad_route(int dtype, int nprob, const int* N, const int* Kin, int64_t mtok, int flags, int rows_per_scale,
+                    float scale_const, VtxRoute* out);
+int vtx_wattn_route(int dtype, int bwd, int masked, int problems_per_head, int inverse_map, VtxRoute* out);
+/* 1 where the LDS-DMA forward-layout kernels take a [*, K] x [N, K]^T GEMM: a dgrad then runs on the transposed weight copy */
+int vtx_gemm_glds_ok(int N, int K);
+
 /* ---- Fused MLP of the narrow stages (csrc/mlp_fused.hip; reference models/layer.py:186-196 inside models/swin_transformer.py:193-197):
  * bf16, C = 64 / 96, ff % 32 == 0, both weights resident in LDS, >= 32 768 rows (vtx_mlp_fused_ok tells; option MLP_FUSED).
  *   vtx_mlp_fwd: y = resid + rowscale[row / rows_per_scale] * (silu(ln2 . w1^T + b1) . w2^T + b2); z (the bf16 pre-activation) and

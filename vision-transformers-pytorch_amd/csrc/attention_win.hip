@@ -27,6 +27,7 @@
 
 #include "options.h"
 #include "vtx_common.h"
+#include "../../include/vtx.h"    // (VtxRoute; after the internal header, as in layer.hip)
 
 #define WA_D 32
 #define WA_LP 64
@@ -1106,14 +1107,35 @@ template <typename K> static int wa_smem_attr(K kern, int bytes) {
   return VTX_OK;
 }
 
-template <typename T, bool MASKED>
-static int wattn_fwd_launch(const void* qkv, void* o, float* lse, const float* rel_pos, const int64_t* pos,
-                            const uint8_t* region, int nbn, const WinGeom& g, hipStream_t st) {
-  if constexpr (sizeof(T) == 2) {
+// Which kernel a window-attention launch takes: four waves per problem (bf16 only) or one; decided here, read by the launchers below
+// and by vtx_wattn_route.
+struct WattnRoute { int four, masked, dtype, bwd; };
+static WattnRoute wattn_route(int dtype, bool bwd, bool masked, int nbn, bool inverse_map) {
+  WattnRoute r;
+  r.dtype = dtype; r.bwd = bwd; r.masked = masked; r.four = 0;
+  if (dtype != VTX_BF16) return r;
+  if (bwd) {
+    r.four = inverse_map && vtx_opt(VTX_OPT_WATTN_BWD4) != 0;
+  } else {
     // four waves per problem: measured faster only with many problems per head (Swin-S stage 1, 8 192: 70 vs 75-76 us; stage 3, 512: 23.0-23.8
     // vs 22.5-23.0 us; profiles/round5_wattn_fwd4.txt)
     const int f4 = vtx_opt(VTX_OPT_WATTN_FWD4);
-    if (f4 >= 2 || (f4 == 1 && nbn >= 4096)) {
+    r.four = f4 >= 2 || (f4 == 1 && nbn >= 4096);
+  }
+  return r;
+}
+static void wattn_route_label(const WattnRoute& r, char* buf, size_t n) {
+  const char* d = r.bwd ? "bwd" : "fwd";
+  const char* m = r.masked ? "true" : "false";
+  if (r.four) snprintf(buf, n, "wattn_%s4_kernel<%s>", d, m);
+  else snprintf(buf, n, "wattn_%s_kernel<%s, %s>", d, r.dtype == VTX_BF16 ? "__bf16" : "float", m);
+}
+
+template <typename T, bool MASKED>
+static int wattn_fwd_launch(const WattnRoute& r, const void* qkv, void* o, float* lse, const float* rel_pos, const int64_t* pos,
+                            const uint8_t* region, int nbn, const WinGeom& g, hipStream_t st) {
+  if constexpr (sizeof(T) == 2) {
+    if (r.four) {
       const int nb4 = wattn_fwd4_blocks(nbn, g.nH);
       hipLaunchKernelGGL(wattn_fwd4_kernel<MASKED>, dim3(nb4 * g.nH), dim3(64 * WA_WAVES), Wf4Smem::kTotal, st,
                          (const bf16*)qkv, (bf16*)o, lse, rel_pos, pos, region, nbn, nb4, wattn_xcd_major(nb4),
@@ -1129,14 +1151,25 @@ static int wattn_fwd_launch(const void* qkv, void* o, float* lse, const float* r
                      (const T*)qkv, (T*)o, lse, rel_pos, pos, region, nbn, nblk, wattn_xcd_major(nblk), vtx_opt(VTX_OPT_WATTN_FAST), g);
   return vtx_check_launch();
 }
+static int wattn_fwd_routed(int dtype, const void* qkv, void* o, float* lse, const float* rel_pos, const int64_t* pos,
+                            const uint8_t* region, int nbn, const WinGeom& g, hipStream_t st) {
+  const WattnRoute r = wattn_route(dtype, false, region != nullptr, nbn, false);
+  if (dtype == VTX_BF16)
+    return r.masked ? wattn_fwd_launch<bf16, true>(r, qkv, o, lse, rel_pos, pos, region, nbn, g, st)
+                    : wattn_fwd_launch<bf16, false>(r, qkv, o, lse, rel_pos, pos, region, nbn, g, st);
+  if (dtype == VTX_F32)
+    return r.masked ? wattn_fwd_launch<float, true>(r, qkv, o, lse, rel_pos, pos, region, nbn, g, st)
+                    : wattn_fwd_launch<float, false>(r, qkv, o, lse, rel_pos, pos, region, nbn, g, st);
+  return VTX_ERR_DTYPE;
+}
 
 template <typename T, bool MASKED>
-static int wattn_bwd_launch(const void* qkv, const void* o, const void* dout, const float* lse, const float* rel_pos,
+static int wattn_bwd_launch(const WattnRoute& r, const void* qkv, const void* o, const void* dout, const float* lse, const float* rel_pos,
                             const int64_t* pos, const uint8_t* region, void* dqkv, float* part, const int* inv_cells,
                             int inv_count, int nbn, const WinGeom& g, hipStream_t st) {
   const int rows = wattn_bwd_rows(nbn, g.nH);
   if constexpr (sizeof(T) == 2) {
-    if (inv_cells != nullptr && vtx_opt(VTX_OPT_WATTN_BWD4) != 0) {   // four waves per problem
+    if (r.four) {
       auto kern4 = wattn_bwd4_kernel<MASKED>;
       int rc4 = wa_smem_attr(kern4, Wa4Smem::kTotal);
       if (rc4) return rc4;
@@ -1161,6 +1194,19 @@ static int wattn_bwd_launch(const void* qkv, const void* o, const void* dout, co
   return vtx_check_launch();
 }
 
+static int wattn_bwd_routed(int dtype, const void* qkv, const void* o, const void* dout, const float* lse, const float* rel_pos,
+                            const int64_t* pos, const uint8_t* region, void* dqkv, float* part, const int* inv_cells,
+                            int inv_count, int nbn, const WinGeom& g, hipStream_t st) {
+  const WattnRoute r = wattn_route(dtype, true, region != nullptr, nbn, inv_cells != nullptr);
+  if (dtype == VTX_BF16)
+    return r.masked ? wattn_bwd_launch<bf16, true>(r, qkv, o, dout, lse, rel_pos, pos, region, dqkv, part, inv_cells, inv_count, nbn, g, st)
+                    : wattn_bwd_launch<bf16, false>(r, qkv, o, dout, lse, rel_pos, pos, region, dqkv, part, inv_cells, inv_count, nbn, g, st);
+  if (dtype == VTX_F32)
+    return r.masked ? wattn_bwd_launch<float, true>(r, qkv, o, dout, lse, rel_pos, pos, region, dqkv, part, inv_cells, inv_count, nbn, g, st)
+                    : wattn_bwd_launch<float, false>(r, qkv, o, dout, lse, rel_pos, pos, region, dqkv, part, inv_cells, inv_count, nbn, g, st);
+  return VTX_ERR_DTYPE;
+}
+
 extern "C" {
 
 /* Window attention (head dim 32, window <= 64 tokens) -- the Swin path (reference swin_transformer.py:103-160).
@@ -1177,13 +1223,7 @@ int vtx_wattn_fwd(const void* qkv, void* o, float* lse, const float* rel_pos, co
   const int nbn = B * g.nW;
   if (nbn <= 0) return VTX_OK;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == VTX_BF16)
-    return region ? wattn_fwd_launch<bf16, true>(qkv, o, lse, rel_pos, pos, region, nbn, g, st)
-                  : wattn_fwd_launch<bf16, false>(qkv, o, lse, rel_pos, pos, region, nbn, g, st);
-  if (dtype == VTX_F32)
-    return region ? wattn_fwd_launch<float, true>(qkv, o, lse, rel_pos, pos, region, nbn, g, st)
-                  : wattn_fwd_launch<float, false>(qkv, o, lse, rel_pos, pos, region, nbn, g, st);
-  return VTX_ERR_DTYPE;
+  return wattn_fwd_routed(dtype, qkv, o, lse, rel_pos, pos, region, nbn, g, st);
 }
 
 /* The same over Bk <= B images only: the b-th one is image perm[b] (perm [B] int32 on the device: the kept samples of a
@@ -1199,13 +1239,7 @@ int vtx_wattn_fwd_mapped(const void* qkv, void* o, float* lse, const float* rel_
   const int nbn = Bk * g.nW;
   if (nbn <= 0) return VTX_OK;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == VTX_BF16)
-    return region ? wattn_fwd_launch<bf16, true>(qkv, o, lse, rel_pos, pos, region, nbn, g, st)
-                  : wattn_fwd_launch<bf16, false>(qkv, o, lse, rel_pos, pos, region, nbn, g, st);
-  if (dtype == VTX_F32)
-    return region ? wattn_fwd_launch<float, true>(qkv, o, lse, rel_pos, pos, region, nbn, g, st)
-                  : wattn_fwd_launch<float, false>(qkv, o, lse, rel_pos, pos, region, nbn, g, st);
-  return VTX_ERR_DTYPE;
+  return wattn_fwd_routed(dtype, qkv, o, lse, rel_pos, pos, region, nbn, g, st);
 }
 
 /* partial rows ([rows][172 * nH] fp32, the first (2 win - 1)^2 * nH columns used) vtx_wattn_bwd leaves in its workspace when
@@ -1239,13 +1273,7 @@ int vtx_wattn_bwd(const void* qkv, const void* o, const void* dout, const float*
   if (inv_cells != nullptr && (inv_count <= 0 || inv_count > L * L)) return VTX_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   float* part = (float*)workspace;
-  if (dtype == VTX_BF16)
-    rc = region ? wattn_bwd_launch<bf16, true>(qkv, o, dout, lse, rel_pos, pos, region, dqkv, part, inv_cells, inv_count, nbn, g, st)
-                : wattn_bwd_launch<bf16, false>(qkv, o, dout, lse, rel_pos, pos, region, dqkv, part, inv_cells, inv_count, nbn, g, st);
-  else if (dtype == VTX_F32)
-    rc = region ? wattn_bwd_launch<float, true>(qkv, o, dout, lse, rel_pos, pos, region, dqkv, part, inv_cells, inv_count, nbn, g, st)
-                : wattn_bwd_launch<float, false>(qkv, o, dout, lse, rel_pos, pos, region, dqkv, part, inv_cells, inv_count, nbn, g, st);
-  else return VTX_ERR_DTYPE;
+  rc = wattn_bwd_routed(dtype, qkv, o, dout, lse, rel_pos, pos, region, dqkv, part, inv_cells, inv_count, nbn, g, st);
   if (rc || drel_pos == nullptr) return rc;              // deferred: partials stay in the workspace
   const int ntab = (2 * win - 1) * (2 * win - 1);
   const int nwaves = wattn_bwd_rows(nbn, nH);
@@ -1271,13 +1299,19 @@ int vtx_wattn_bwd_mapped(const void* qkv, const void* o, const void* dout, const
   if (inv_cells != nullptr && (inv_count <= 0 || inv_count > L * L)) return VTX_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   float* part = (float*)workspace;
-  if (dtype == VTX_BF16)
-    return region ? wattn_bwd_launch<bf16, true>(qkv, o, dout, lse, rel_pos, pos, region, dqkv, part, inv_cells, inv_count, nbn, g, st)
-                  : wattn_bwd_launch<bf16, false>(qkv, o, dout, lse, rel_pos, pos, region, dqkv, part, inv_cells, inv_count, nbn, g, st);
-  if (dtype == VTX_F32)
-    return region ? wattn_bwd_launch<float, true>(qkv, o, dout, lse, rel_pos, pos, region, dqkv, part, inv_cells, inv_count, nbn, g, st)
-                  : wattn_bwd_launch<float, false>(qkv, o, dout, lse, rel_pos, pos, region, dqkv, part, inv_cells, inv_count, nbn, g, st);
-  return VTX_ERR_DTYPE;
+  return wattn_bwd_routed(dtype, qkv, o, dout, lse, rel_pos, pos, region, dqkv, part, inv_cells, inv_count, nbn, g, st);
+}
+
+/* The kernel instantiation a window-attention launch of this shape takes under the current options (include/vtx.h); launches nothing. */
+int vtx_wattn_route(int dtype, int bwd, int masked, int problems_per_head, int inverse_map, VtxRoute* out) {
+  if (!out) return VTX_ERR_NULL;
+  if (dtype != VTX_BF16 && dtype != VTX_F32) return VTX_ERR_DTYPE;
+  const WattnRoute r = wattn_route(dtype, bwd != 0, masked != 0, problems_per_head, inverse_map != 0);
+  *out = VtxRoute{};
+  out->family = r.four ? 2 : 1;
+  out->waves = r.four ? 4 : 1;
+  wattn_route_label(r, out->label, sizeof(out->label));
+  return VTX_OK;
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@
 // Workgroup ids are remapped so that tiles sharing an operand panel run on the same XCD (private L2).
 #include "gemm_common.h"
 #include "options.h"
+#include "../../include/vtx.h"    // (VtxRoute, VtxGemmQuery; after the internal header, as in layer.hip)
 
 template <typename T> struct GemmGeom {
   static constexpr int BK = 128 / (int)sizeof(T);      // elements per LDS k-tile row
@@ -244,12 +245,78 @@ static int gemm_launch(const GemmArgs& a, int nz, hipStream_t st) {
   return vtx_check_launch();
 }
 
+// register-staged kernels: every mode and dtype, 128 x BN tiles by N
+static void gemm_reg_route(const GemmArgs& a, int mode, int dtype, GemmRoute& r) {
+  r.family = GEMM_FAM_REG;
+  r.mode = mode; r.dtype = dtype;
+  r.bm = 128;
+  r.bn = a.N % 128 == 0 ? 128 : (a.N % 96 == 0 ? 96 : (a.N <= 64 ? 64 : 128));
+}
+
 template <typename T, typename TO, bool TA, bool TB>
-static int gemm_pick_bn(const GemmArgs& a, int nz, hipStream_t st) {
-  if (a.N % 128 == 0) return gemm_launch<T, TO, 128, TA, TB>(a, nz, st);
-  if (a.N % 96 == 0) return gemm_launch<T, TO, 96, TA, TB>(a, nz, st);
-  if (a.N <= 64) return gemm_launch<T, TO, 64, TA, TB>(a, nz, st);
-  return gemm_launch<T, TO, 128, TA, TB>(a, nz, st);
+static int gemm_launch_bn(const GemmArgs& a, const GemmRoute& r, int nz, hipStream_t st) {
+  switch (r.bn) {
+    case 128: return gemm_launch<T, TO, 128, TA, TB>(a, nz, st);
+    case 96: return gemm_launch<T, TO, 96, TA, TB>(a, nz, st);
+    case 64: return gemm_launch<T, TO, 64, TA, TB>(a, nz, st);
+    default: return VTX_ERR_SHAPE;
+  }
+}
+// mode 2: the weight gradient (TA, TB, fp32 out, nz split-K slices)
+static int gemm_reg_launch(const GemmArgs& a, const GemmRoute& r, int nz, hipStream_t st) {
+  if (r.dtype == VTX_BF16) {
+    if (r.mode == 2) return gemm_launch_bn<bf16, float, true, true>(a, r, nz, st);
+    return r.mode == 0 ? gemm_launch_bn<bf16, bf16, false, false>(a, r, nz, st) : gemm_launch_bn<bf16, bf16, false, true>(a, r, nz, st);
+  }
+  if (r.mode == 2) return gemm_launch_bn<float, float, true, true>(a, r, nz, st);
+  return r.mode == 0 ? gemm_launch_bn<float, float, false, false>(a, r, nz, st) : gemm_launch_bn<float, float, false, true>(a, r, nz, st);
+}
+static void gemm_reg_label(const GemmRoute& r, char* buf, size_t n) {
+  const char* t = r.dtype == VTX_BF16 ? "__bf16" : "float";
+  snprintf(buf, n, "gemm_kernel<%s, %s, 128, %d, %s, %s>", t, r.mode == 2 ? "float" : t, r.bn, r.mode == 2 ? "true" : "false",
+           r.mode == 0 ? "false" : "true");
+}
+
+// THE routing decision of a GEMM launch (mode 0 | 1: vtx_gemm and the row-mapped launches of the layers; 2: the register-staged weight
+// gradient).  Pure: reads the arguments' shapes, which operands are present, the options and the CU count.
+int gemm_route(const GemmArgs& a, int mode, int dtype, GemmRoute& r) {
+  r = GemmRoute{};
+  if (dtype != VTX_BF16 && dtype != VTX_F32) return VTX_ERR_DTYPE;
+  if (dtype == VTX_BF16 && mode == 0) {
+    if (gemm_skinny_route(a, r)) return VTX_OK;
+    // (a row-mapped launch exists on the LDS-DMA kernels only: gemm_mapped_validate has admitted it)
+    if (gemm_glds_ok(a.N, a.K) && (gemm_glds_enabled() || a.perm != nullptr)) {
+      if (gemm_pp_route(a, r) || gemm_astat_route(a, r)) return VTX_OK;
+      gemm_glds_route(a, r);
+      return VTX_OK;
+    }
+  }
+  gemm_reg_route(a, mode, dtype, r);
+  return VTX_OK;
+}
+
+int gemm_route_launch(const GemmArgs& a, const GemmRoute& r, int nz, hipStream_t st) {
+  switch (r.family) {
+    case GEMM_FAM_SKINNY: return gemm_skinny_launch(a, r, st);
+    case GEMM_FAM_PP: return gemm_pp_launch(a, r, st);
+    case GEMM_FAM_ASTAT: return gemm_astat_launch(a, r, st);
+    case GEMM_FAM_GLDS_PV:
+    case GEMM_FAM_GLDS: return gemm_glds_launch(a, r, st);
+    case GEMM_FAM_REG: return gemm_reg_launch(a, r, nz, st);
+    default: return VTX_ERR_SHAPE;
+  }
+}
+
+void gemm_route_label(const GemmRoute& r, char* buf, size_t n) {
+  switch (r.family) {
+    case GEMM_FAM_SKINNY: return gemm_skinny_label(r, buf, n);
+    case GEMM_FAM_PP: return gemm_pp_label(r, buf, n);
+    case GEMM_FAM_ASTAT: return gemm_astat_label(r, buf, n);
+    case GEMM_FAM_GLDS_PV:
+    case GEMM_FAM_GLDS: return gemm_glds_label(r, buf, n);
+    case GEMM_FAM_REG: return gemm_reg_label(r, buf, n);
+    default: snprintf(buf, n, "none");
+  }
 }
 
 static int gemm_validate(const GemmArgs& a, int mode) {
@@ -261,6 +328,21 @@ static int gemm_validate(const GemmArgs& a, int mode) {
   if (mode == 2 && (a.M & 7)) return VTX_ERR_ALIGN;                   // A^T[k][m] rows
   if ((a.act == 2 || a.act == 4) && !a.aux_in) return VTX_ERR_NULL;
   return VTX_OK;
+}
+
+// Route of ONE weight gradient (vtx_wgrad; a = its GemmArgs: M = N, N = Kin, K = tokens, kchunk and k_per_scale set): the LDS-DMA kernel on
+// 128 x 128 tiles where wgrad_glds_ok admits the shape, else the register-staged TA kernel.
+// (the LDS-DMA kernel keeps the DropPath liveness of a slice's samples in a 512-entry table: slices spanning more
+//  samples -- sequences of one or two tokens -- take the register-staged kernel)
+static int wgrad_single_route(const GemmArgs& a, int dtype, bool has_rowscale, WgradRoute& r) {
+  static const float one = 1.f;
+  r = WgradRoute{};
+  if (wgrad_glds_ok(dtype, a.M, a.N, has_rowscale ? &one : nullptr, a.kscale_const) && (!has_rowscale || a.kchunk / a.k_per_scale + 2 <= 512)) {
+    wgrad_glds_route(false, r);
+    return VTX_OK;
+  }
+  r.family = WGRAD_FAM_REG;
+  return gemm_route(a, 2, dtype, r.reg);
 }
 
 extern "C" {
@@ -280,16 +362,10 @@ int vtx_gemm(int mode, int dtype, const void* A, const void* B, void* C, int M, 
   if (act < 0 || act > 4) return VTX_ERR_SHAPE;
   int rc = gemm_validate(a, mode);
   if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == VTX_BF16 && mode == 0 && gemm_skinny_ok(a)) return gemm_skinny_launch(a, st);
-  if (dtype == VTX_BF16 && mode == 0 && gemm_glds_ok(N, K) && gemm_glds_enabled()) {
-    return gemm_glds_launch(a, st);
-  }
-  if (dtype == VTX_BF16)
-    return mode == 0 ? gemm_pick_bn<bf16, bf16, false, false>(a, 1, st) : gemm_pick_bn<bf16, bf16, false, true>(a, 1, st);
-  if (dtype == VTX_F32)
-    return mode == 0 ? gemm_pick_bn<float, float, false, false>(a, 1, st) : gemm_pick_bn<float, float, false, true>(a, 1, st);
-  return VTX_ERR_DTYPE;
+  GemmRoute r;
+  rc = gemm_route(a, mode, dtype, r);
+  if (rc) return rc;
+  return gemm_route_launch(a, r, 1, (hipStream_t)stream);
 }
 
 // Number of contraction slices (split-K over tokens) of the register-staged wgrad kernels: tiles x slices should just
@@ -356,19 +432,17 @@ int vtx_wgrad(int dtype, const void* dy, const void* x, float* dW, float* dbias,
   a.ksum_out = dbias ? (nz == 1 ? dbias : bias_part) : nullptr;
   int rc = gemm_validate(a, 2);
   if (rc) return rc;
-  // (the LDS-DMA kernel keeps the DropPath liveness of a slice's samples in a 512-entry table: slices spanning more
-  //  samples -- sequences of one or two tokens -- take the register-staged kernel)
-  if (wgrad_glds_ok(dtype, N, Kin, rowscale, scale_const) && (rowscale == nullptr || a.kchunk / a.k_per_scale + 2 <= 512)) {
+  WgradRoute r;
+  rc = wgrad_single_route(a, dtype, rowscale != nullptr, r);
+  if (rc) return rc;
+  if (r.family == WGRAD_FAM_REG) {
+    rc = gemm_route_launch(a, r.reg, nz, st);
+  } else {
     WgradProbHost hp;
     hp.dy = dy; hp.x = x; hp.slab = (float*)workspace; hp.out = dW; hp.ksum_part = bias_part; hp.ksum_out = dbias;
     hp.rowscale = rowscale; hp.ld_dy = ld_dy; hp.ld_x = ld_x; hp.N = N; hp.Kin = Kin; hp.live_only = 0; hp.perm = nullptr; hp.Mtok = (int)mtok; hp.scale = 1.f;
-    rc = wgrad_glds_group_launch(1, &hp, mtok, a.k_per_scale, scale_const, nz, a.kchunk, st);
-    if (rc || nz == 1) return rc;
-    return reduce_slabs((const float*)workspace, bias_part, dW, dbias, N, Kin, nz, st);
+    rc = wgrad_glds_group_launch(1, &hp, mtok, a.k_per_scale, scale_const, nz, a.kchunk, st, r);
   }
-  if (dtype == VTX_BF16) rc = gemm_pick_bn<bf16, float, true, true>(a, nz, st);
-  else if (dtype == VTX_F32) rc = gemm_pick_bn<float, float, true, true>(a, nz, st);
-  else return VTX_ERR_DTYPE;
   if (rc || nz == 1) return rc;
   return reduce_slabs((const float*)workspace, bias_part, dW, dbias, N, Kin, nz, st);
 }
@@ -399,16 +473,14 @@ static int group_tiles(int nprob, const int* N, const int* Kin) {
 }
 
 // slices of a group under the current options: 128 x 384 tiles (wgrad_wide_tiles) or 128 x 128
-static int group_slices(int nprob, const int* N, const int* Kin, int64_t mtok, int* wide) {
-  int J = 0;
-  const int wt = wgrad_wide_tiles(nprob, N, Kin, &J);
-  if (wide) *wide = wt > 0 ? J : 0;
+static int group_slices(int nprob, const int* N, const int* Kin, int64_t mtok) {
+  const int wt = wgrad_wide_tiles(nprob, N, Kin);
   return wt ? wgrad_glds_slices(mtok, wt, true) : wgrad_glds_slices(mtok, group_tiles(nprob, N, Kin));
 }
 
 int vtx_wgrad_group_slices(int nprob, const int* N, const int* Kin, int64_t mtok) {
   if (nprob < 1 || nprob > wgrad_glds_max_problems() || !N || !Kin || mtok <= 0) return 0;
-  return group_slices(nprob, N, Kin, mtok, nullptr);
+  return group_slices(nprob, N, Kin, mtok);
 }
 
 size_t vtx_wgrad_group_workspace(int nprob, const int* N, const int* Kin, int64_t mtok) {
@@ -456,8 +528,7 @@ int vtx_wgrad_group_mapped(int dtype, int nprob, const void* const* dy, const vo
   if (!vtx_wgrad_group_ok(dtype, nprob, N, Kin, mtok, any_scale, rows_per_scale, scale_const)) return VTX_ERR_SHAPE;
   if (ws_bytes < vtx_wgrad_group_workspace(nprob, N, Kin, mtok)) return VTX_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  int wide = 0;
-  const int nz = group_slices(nprob, N, Kin, mtok, &wide);
+  const int nz = group_slices(nprob, N, Kin, mtok);
   if (accumulate && nz < 2) return VTX_ERR_SHAPE;          // accumulation lives in the slab reduce (vtx_wgrad_group_slices tells)
   WgradProbHost hp[8];
   float* w = (float*)workspace;
@@ -483,7 +554,11 @@ int vtx_wgrad_group_mapped(int dtype, int nprob, const void* const* dy, const vo
   int64_t mmax = 0;                                         // (mapped problems contract over their kept tokens only)
   for (int i = 0; i < nprob; ++i) mmax = hp[i].Mtok > mmax ? hp[i].Mtok : mmax;
   const int kchunk = (int)chunk_of(mmax, nz);
-  int rc = wgrad_glds_group_launch(nprob, hp, mmax, rows_per_scale, scale_const, nz, kchunk, st, wide);
+  bool mapped = false;
+  for (int i = 0; i < nprob; ++i) mapped = mapped || hp[i].perm != nullptr;
+  WgradRoute r;
+  wgrad_group_route(nprob, N, Kin, mapped, r);
+  int rc = wgrad_glds_group_launch(nprob, hp, mmax, rows_per_scale, scale_const, nz, kchunk, st, r);
   if (rc || (nz == 1 && ncol == 0)) return rc;
   // ONE reduction launch behind the group: all weight and bias slabs (kernel boundary = visibility: the slabs were written
   // with plain stores) and the layer's deferred column reductions (LayerNorm dgamma / dbeta, rel_pos gradient)
@@ -516,5 +591,86 @@ int vtx_wgrad_group_mapped(int dtype, int nprob, const void* const* dy, const vo
   hipLaunchKernelGGL(layer_reduce_kernel, dim3((unsigned)m.cblk0[4]), dim3(1024), 0, st, m);
   return vtx_check_launch();
 }
+
+// ---- routing queries (include/vtx.h): the decision of gemm_route / wgrad_*_route for a launch described by shape, with its name
+static void route_out(const GemmRoute& r, VtxRoute* out) {
+  *out = VtxRoute{};
+  out->family = r.family;
+  out->tile_m = r.bm; out->tile_n = r.bn; out->tile_k = r.bk; out->stages = r.stages;
+  out->waves = r.family == GEMM_FAM_SKINNY ? r.waves : r.nwn;
+  out->wmf = r.wmf; out->nf = r.nf; out->ktiles = r.nkt;
+  out->mapped = r.mapped; out->act = r.act; out->resid = r.resid; out->aux = r.aux;
+  gemm_route_label(r, out->label, sizeof(out->label));
+}
+
+int vtx_gemm_route(const VtxGemmQuery* q, VtxRoute* out) {
+  if (!q || !out) return VTX_ERR_NULL;
+  if (q->mode < 0 || q->mode > 2 || q->act < 0 || q->act > 4 || q->M <= 0 || q->N <= 0 || q->K <= 0) return VTX_ERR_SHAPE;
+  // the arguments the launch would see: contiguous operands, a non-null stand-in for every operand that is present (never dereferenced)
+  static const float one = 1.f;
+  static const int zero = 0;
+  static char opA, opB, opC, opR, opZ;
+  const bool wg = q->mode == 2;
+  GemmArgs a = {};
+  a.A = &opA; a.B = &opB; a.C = &opC;
+  a.M = q->M; a.N = q->N; a.K = q->K;
+  a.lda = wg ? q->M : q->K; a.ldb = q->mode == 0 ? q->K : q->N; a.ldc = q->N;
+  a.bias = (q->flags & VTX_Q_BIAS) ? &one : nullptr;
+  a.resid = (q->flags & VTX_Q_INPLACE) ? (const void*)&opC : ((q->flags & VTX_Q_RESID) ? (const void*)&opR : nullptr);
+  a.rowscale = (q->flags & VTX_Q_ROWSCALE) ? &one : nullptr;
+  a.rows_per_scale = q->rows_per_scale > 0 ? q->rows_per_scale : 1;
+  a.aux_out = (q->flags & VTX_Q_AUXOUT) ? (void*)&opZ : nullptr;
+  a.aux_in = (q->flags & VTX_Q_AUXIN) ? (const void*)&opZ : nullptr;
+  a.act = q->act; a.k_per_scale = 1;
+  a.kchunk = ((q->K + 127) / 128) * 128;
+  gemm_args_nomap(a);
+  if (q->flags & VTX_Q_MAPPED) {
+    if (wg) return VTX_ERR_SHAPE;
+    a.perm = &zero; a.Mk = q->Mk > 0 ? q->Mk : q->M;
+    if (q->map_T > 0) {
+      a.map_T = q->map_T; a.map_magic = vtx_div_magic(q->map_T);
+      if (a.rowscale) a.rows_per_scale = q->map_T;
+      const int rc = gemm_mapped_validate(a);
+      if (rc) return rc;
+    } else {                                                   // (rows per sample unknown: one sample of Mk rows; the launch itself was validated)
+      a.M = a.Mk; a.map_T = a.Mk; a.rows_per_scale = a.Mk;
+    }
+  }
+  GemmRoute r;
+  const int rc = gemm_route(a, q->mode, q->dtype, r);
+  if (rc) return rc;
+  route_out(r, out);
+  return VTX_OK;
+}
+
+int vtx_wgrad_route(int dtype, int nprob, const int* N, const int* Kin, int64_t mtok, int flags, int rows_per_scale,
+                    float scale_const, VtxRoute* out) {
+  if (!N || !Kin || !out) return VTX_ERR_NULL;
+  if (nprob < 1 || nprob > wgrad_glds_max_problems() || mtok <= 0 || mtok > 0x7fffffff) return VTX_ERR_SHAPE;
+  WgradRoute r;
+  if (flags & 1) {
+    wgrad_group_route(nprob, N, Kin, (flags & 4) != 0, r);
+  } else {
+    if (nprob != 1) return VTX_ERR_SHAPE;
+    const int nz = wgrad_slices(mtok, N[0], Kin[0]);
+    GemmArgs a = {};
+    a.M = N[0]; a.N = Kin[0]; a.K = (int)mtok;
+    a.k_per_scale = rows_per_scale > 0 ? rows_per_scale : 1; a.kscale_const = scale_const;
+    a.kchunk = (int)chunk_of(mtok, nz);
+    const int rc = wgrad_single_route(a, dtype, (flags & 2) != 0, r);
+    if (rc) return rc;
+  }
+  if (r.family == WGRAD_FAM_REG) {
+    route_out(r.reg, out);
+  } else {
+    *out = VtxRoute{};
+    out->waves = r.waves; out->mapped = r.mapped; out->wide_j = r.wide_j; out->tiles = r.tiles;
+    wgrad_route_label(r, out->label, sizeof(out->label));
+  }
+  out->family = r.family;
+  return VTX_OK;
+}
+
+int vtx_gemm_glds_ok(int N, int K) { return gemm_glds_ok(N, K) ? 1 : 0; }
 
 }  // extern "C"

@@ -567,7 +567,7 @@ static size_t astat_smem(int K) { return (size_t)(K / 64 + AS_NSW) * AS_KT_BYTES
 
 static int astat_cus() { return vtx_cu_count_cached(); }
 
-bool gemm_astat_ok(const GemmArgs& a) {
+static bool gemm_astat_ok(const GemmArgs& a) {
   const int mode = vtx_opt(VTX_OPT_GEMM_ASTAT);
   if (mode == 0) return false;
   if (a.K % 64 != 0 || a.K < 192 || a.K > 384 || a.N % 64 != 0 || a.N < 256 || (a.N > AS_MAXN && a.bias != nullptr)) return false;
@@ -609,27 +609,41 @@ template <int NKT, bool MAPPED, int ACT, bool RESID, bool AUX> static int astat_
   hipLaunchKernelGGL(kern, dim3(sc.nwg), dim3(AS_NT), smem, st, a, sc);
   return vtx_check_launch();
 }
-template <int NKT, bool MAPPED> static int astat_launch_m(const GemmArgs& a, hipStream_t st) {
-  const bool aux = a.aux_out != nullptr;
-  switch (a.act) {
-    case 0: return a.resid != nullptr ? astat_launch_k<NKT, MAPPED, 0, true, false>(a, st) : astat_launch_k<NKT, MAPPED, 0, false, false>(a, st);
-    case 1: return aux ? astat_launch_k<NKT, MAPPED, 1, false, true>(a, st) : astat_launch_k<NKT, MAPPED, 1, false, false>(a, st);
+bool gemm_astat_route(const GemmArgs& a, GemmRoute& r) {
+  if (!gemm_astat_ok(a)) return false;
+  r.family = GEMM_FAM_ASTAT;
+  r.nkt = a.K / 64;
+  r.mapped = a.perm != nullptr;
+  r.act = a.act;
+  r.resid = a.act == 0 && a.resid != nullptr;
+  r.aux = (a.act == 1 || a.act == 3) && a.aux_out != nullptr;
+  return true;
+}
+
+template <int NKT, bool MAPPED> static int astat_launch_m(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
+  switch (r.act) {
+    case 0: return r.resid ? astat_launch_k<NKT, MAPPED, 0, true, false>(a, st) : astat_launch_k<NKT, MAPPED, 0, false, false>(a, st);
+    case 1: return r.aux ? astat_launch_k<NKT, MAPPED, 1, false, true>(a, st) : astat_launch_k<NKT, MAPPED, 1, false, false>(a, st);
     case 2: return astat_launch_k<NKT, MAPPED, 2, false, false>(a, st);
-    case 3: return aux ? astat_launch_k<NKT, MAPPED, 3, false, true>(a, st) : astat_launch_k<NKT, MAPPED, 3, false, false>(a, st);
+    case 3: return r.aux ? astat_launch_k<NKT, MAPPED, 3, false, true>(a, st) : astat_launch_k<NKT, MAPPED, 3, false, false>(a, st);
     case 4: return astat_launch_k<NKT, MAPPED, 4, false, false>(a, st);
     default: return VTX_ERR_SHAPE;
   }
 }
-template <int NKT> static int astat_launch_n(const GemmArgs& a, hipStream_t st) {
-  return a.perm != nullptr ? astat_launch_m<NKT, true>(a, st) : astat_launch_m<NKT, false>(a, st);
+template <int NKT> static int astat_launch_n(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
+  return r.mapped ? astat_launch_m<NKT, true>(a, r, st) : astat_launch_m<NKT, false>(a, r, st);
 }
 
-int gemm_astat_launch(const GemmArgs& a, hipStream_t st) {
-  switch (a.K / 64) {
-    case 3: return astat_launch_n<3>(a, st);
-    case 4: return astat_launch_n<4>(a, st);
-    case 5: return astat_launch_n<5>(a, st);
-    case 6: return astat_launch_n<6>(a, st);
+int gemm_astat_launch(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
+  switch (r.nkt) {
+    case 3: return astat_launch_n<3>(a, r, st);
+    case 4: return astat_launch_n<4>(a, r, st);
+    case 5: return astat_launch_n<5>(a, r, st);
+    case 6: return astat_launch_n<6>(a, r, st);
     default: return VTX_ERR_SHAPE;
   }
+}
+// (the name tools and tests know: k-tiles and the row map; the epilogue arguments stay "...")
+void gemm_astat_label(const GemmRoute& r, char* buf, size_t n) {
+  snprintf(buf, n, "gemm_astat_kernel<%d, %s, ...>", r.nkt, r.mapped ? "true" : "false");
 }

@@ -1,6 +1,7 @@
 // Shared pieces of the GEMM family (gemm.hip: register-staged kernels for every mode / dtype;
 // gemm_glds.hip: LDS-DMA kernel for the bf16 forward-layout GEMMs).
 #pragma once
+#include <stdio.h>
 #include "vtx_common.h"
 
 // phase time stamps for tools/probe/gemm_trace.hip (compiled out of the library)
@@ -168,19 +169,41 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[BM
   }
 }
 
-// LDS-DMA (global_load_lds) bf16 kernel for C = epi(A W^T) with K % 64 == 0 (gemm_glds.hip)
-int gemm_glds_launch(const GemmArgs& a, hipStream_t st);
+// ---- Routing: which kernel instantiation a launch takes is decided ONCE, by gemm_route (gemm.hip), as a small POD; the launchers switch on
+// it and on nothing else, and the query entries (vtx_gemm_route, vtx_wgrad_route, vtx_wattn_route) format the instantiation's name from it.
+// Order of preference: skinny, two-group (pp), A-stationary, tiled LDS-DMA, register-staged.
+enum { GEMM_FAM_NONE = 0, GEMM_FAM_SKINNY = 1, GEMM_FAM_PP = 2, GEMM_FAM_ASTAT = 3, GEMM_FAM_GLDS_PV = 4, GEMM_FAM_GLDS = 5, GEMM_FAM_REG = 6 };
+struct GemmRoute {
+  int family;
+  int bm, bn, bk, stages, nwn;    // tile, k-depth, ring stages, waves along N (GLDS / GLDS_PV; REG: 128 x bn)
+  int wmf, nf;                    // PP: tile height in 32-row units, 16-column accumulator tiles per wave (tile width / 64)
+  int nkt;                        // k-tiles of the whole contraction: ASTAT K / 64, SKINNY K / 32
+  int waves;                      // SKINNY: waves per workgroup
+  int mapped, act, resid, aux;    // what the family templates on (resid: SKINNY's VEC = a vector read per output vector)
+  int mode, dtype;                // REG: transposes and element types
+};
+int gemm_route(const GemmArgs& a, int mode, int dtype, GemmRoute& r);
+int gemm_route_launch(const GemmArgs& a, const GemmRoute& r, int nz, hipStream_t st);
+void gemm_route_label(const GemmRoute& r, char* buf, size_t n);          // (query path only: no launch formats a string)
+// the parts of gemm_route, each next to its family's kernels: false = not this family's launch (r untouched)
+// gemm_glds.hip: LDS-DMA (global_load_lds) bf16 kernels for C = epi(A W^T) with K % 64 == 0
 bool gemm_glds_enabled();
 bool gemm_glds_ok(int N, int K);
+void gemm_glds_route(const GemmArgs& a, GemmRoute& r);
+int gemm_glds_launch(const GemmArgs& a, const GemmRoute& r, hipStream_t st);
+void gemm_glds_label(const GemmRoute& r, char* buf, size_t n);
 // gemm_skinny.hip: weight-resident streaming kernel for K = 64 / 96 / 128 over >= 32 768 rows (bf16, A . W^T)
-bool gemm_skinny_ok(const GemmArgs& a);
-int gemm_skinny_launch(const GemmArgs& a, hipStream_t st);
-// gemm_astat.hip: A-stationary kernel for 128 <= K <= 384 (one workgroup per CU keeps its 128-row strip of A in LDS for all column tiles)
-bool gemm_astat_ok(const GemmArgs& a);
-int gemm_astat_launch(const GemmArgs& a, hipStream_t st);
+bool gemm_skinny_route(const GemmArgs& a, GemmRoute& r);
+int gemm_skinny_launch(const GemmArgs& a, const GemmRoute& r, hipStream_t st);
+void gemm_skinny_label(const GemmRoute& r, char* buf, size_t n);
+// gemm_astat.hip: A-stationary kernel for 192 <= K <= 384 (one workgroup per CU keeps its 128-row strip of A in LDS for all column tiles)
+bool gemm_astat_route(const GemmArgs& a, GemmRoute& r);
+int gemm_astat_launch(const GemmArgs& a, const GemmRoute& r, hipStream_t st);
+void gemm_astat_label(const GemmRoute& r, char* buf, size_t n);
 // gemm_pp.hip: BM x 192 tiles, one workgroup per CU, two wave groups half a k-step apart (N % 192 == 0, K % 64 == 0)
-bool gemm_pp_ok(const GemmArgs& a);
-int gemm_pp_launch(const GemmArgs& a, hipStream_t st);
+bool gemm_pp_route(const GemmArgs& a, GemmRoute& r);
+int gemm_pp_launch(const GemmArgs& a, const GemmRoute& r, hipStream_t st);
+void gemm_pp_label(const GemmRoute& r, char* buf, size_t n);
 // mlp_fused.hip: the whole MLP of a C = 64 / 96 layer in one launch each way (both weights resident in LDS)
 bool mlp_fused_ok(int dtype, int64_t M, int C, int ff);
 int mlp_fused_fwd(const void* ln2, const void* w1, const float* b1, const void* w2, const float* b2, const void* resid,
@@ -209,8 +232,8 @@ int dgrad_ln_launch(const void* dy, const void* wt, const void* x, const float* 
                     void* dx, float* part, int part_rows, int64_t M, int C, int K, hipStream_t st);
 extern "C" int vtx_layernorm_bwd_blocks(int64_t rows, int C);
 extern "C" size_t vtx_layernorm_bwd_workspace(int64_t rows, int C);
-// mapped (compacted) launch: bf16, mode 0, N % 128 == 0, K % 64 == 0, wave-private epilogue -- else VTX_ERR_SHAPE
-int gemm_glds_launch_mapped(const GemmArgs& a, hipStream_t st);
+// mapped (compacted) launch: bf16, mode 0, N % 128 == 0, K % 64 == 0, wave-private epilogue -- else VTX_ERR_SHAPE (then gemm_route as any launch)
+int gemm_mapped_validate(const GemmArgs& a);
 
 // LDS-DMA + transpose-read weight-gradient kernel (gemm_wgrad_glds.hip): bf16, N and Kin multiples of 8 and >= 64,
 // rowscale values restricted to {0, scale_const}.  Grouped: up to wgrad_glds_max_problems() weight gradients over the
@@ -233,5 +256,19 @@ int wgrad_glds_tiles(int N, int Kin);
 int wgrad_wide_tiles(int nprob, const int* N, const int* Kin, int* J = nullptr);   // 128 x 64 J tiles of the group (J = 3 .. 6), or 0: the group stays on 128 x 128 tiles
 int wgrad_wide_tiles_any(int nprob, const int* N, const int* Kin, int* J = nullptr);   // the same whatever option WGRAD_WIDE says (workspace sizing)
 int wgrad_glds_slices(int64_t mtok, int ntiles, bool wide = false);
+// route of a (grouped) weight gradient: LDS-DMA 128 x 128 tiles, 128 x 64 J tiles (wide_j = 3 .. 6), or -- single vtx_wgrad only -- the
+// register-staged TA kernel (reg)
+enum { WGRAD_FAM_GLDS = 1, WGRAD_FAM_WIDE = 2, WGRAD_FAM_REG = 3 };
+struct WgradRoute {
+  int family;
+  int wide_j, tiles;  // WIDE: tile width / 64 and the group's tile count
+  int tg;             // WIDE: two wave groups half a k-step apart (384-column tiles only)
+  int waves;          // GLDS: waves per workgroup
+  int mapped;         // the row-mapped instantiation
+  GemmRoute reg;      // REG
+};
+void wgrad_glds_route(bool mapped, WgradRoute& r);       // 128 x 128 tiles whatever the shapes (single vtx_wgrad)
+void wgrad_group_route(int nprob, const int* N, const int* Kin, bool mapped, WgradRoute& r);
+void wgrad_route_label(const WgradRoute& r, char* buf, size_t n);
 int wgrad_glds_group_launch(int nprob, const WgradProbHost* hp, int64_t mtok, int rows_per_scale, float scale_const,
-                            int nz, int kchunk, hipStream_t st, int wide = 0);
+                            int nz, int kchunk, hipStream_t st, const WgradRoute& r);

@@ -486,11 +486,6 @@ template <int BM, int NWN, bool MAPPED> static int glds_launch_pv_m(const GemmAr
   hipLaunchKernelGGL(kern, grid, dim3(512), smem, st, a);
   return vtx_check_launch();
 }
-// (the row map of stochastic-depth compaction is a compile-time variant: the unmapped kernels carry none of its code)
-template <int BM, int NWN> static int glds_launch_pv(const GemmArgs& a, hipStream_t st) {
-  return a.perm != nullptr ? glds_launch_pv_m<BM, NWN, true>(a, st) : glds_launch_pv_m<BM, NWN, false>(a, st);
-}
-
 template <int BM, int BN, int BK, int NS, int NWN = 2> static int glds_launch_cfg(const GemmArgs& a, hipStream_t st) {
   constexpr size_t smem = (size_t)NS * (BM + BN) * BK * 2;
   auto kern = gemm_glds_kernel<BM, BN, BK, NS, NWN>;
@@ -510,19 +505,7 @@ template <int BM, int BN, int BK, int NS, int NWN = 2> static int glds_launch_cf
 // only with 128-column tiles -- a 32-deep tile row is 64 B, one DMA instruction covers 16 rows, and 96 / 4 waves does
 // not split into whole instructions.  Measured (stage 1, K = 96, N = 384): fc1 forward 256 -> 215 us, fc2 dgrad
 // 283 -> 203 us vs the register-staged kernel; N = 96 / 288 shapes stay on the register-staged kernel (faster there).
-template <int BM, int BN> static int glds_launch_t(const GemmArgs& a, hipStream_t st) {
-  if constexpr (BN == 128) {
-    if (a.K % 64 != 0) return glds_launch_cfg<BM, BN, 32, 3>(a, st);
-  }
-  if constexpr (BN == 128) {
-    // 2 x 4 waves: fwd 3.95 -> 3.78, dgrad 3.66 -> 3.55 ms per step on the Swin stage-2..4 shapes, ViT-S/16 4.64 -> 4.38 /
-    // 4.14 -> 4.07 (the activation epilogues gain most); option GLDS_WAVES = 4 keeps the 2 x 2 variant for comparison
-    if (vtx_opt(VTX_OPT_GLDS_EPI) == 1) return glds_launch_pv<BM, BM == 128 ? 2 : 4>(a, st);
-    if (vtx_opt(VTX_OPT_GLDS_WAVES) != 4) return glds_launch_cfg<BM, BN, 64, 2, 4>(a, st);
-  }
-  return glds_launch_cfg<BM, BN, 64, 2>(a, st);
-}
-
+// (gemm_glds_route turns this into numbers, glds_launch_t into an instantiation)
 bool gemm_glds_ok(int N, int K) { return (K % 64) == 0 || ((K % 32) == 0 && (N % 128) == 0); }
 
 // Tile height.  64-row tiles (48 KB of LDS, 3 workgroups per CU) win wherever a launch has few tiles: the per-tile
@@ -548,31 +531,58 @@ static int glds_pick_bm(const GemmArgs& a, int bn) {
   return tiles128 >= 800 ? 128 : 64;
 }
 
-template <int BN> static int glds_launch_bn(const GemmArgs& a, hipStream_t st) {
-  return glds_pick_bm(a, BN) == 64 ? glds_launch_t<64, BN>(a, st) : glds_launch_t<128, BN>(a, st);
-}
-
 bool gemm_glds_enabled() {
   return vtx_opt(VTX_OPT_GEMM_GLDS) != 0;
 }
 
-int gemm_glds_launch_mapped(const GemmArgs& a, hipStream_t st) {
+int gemm_mapped_validate(const GemmArgs& a) {
   if (a.perm == nullptr || a.map_T <= 0 || a.Mk <= 0 || a.Mk > a.M) return VTX_ERR_SHAPE;
   if (a.N % 128 != 0 || a.K % 64 != 0 || vtx_opt(VTX_OPT_GLDS_EPI) != 1) return VTX_ERR_SHAPE;   // wave-private epilogue kernels only
   if (a.rowscale != nullptr && a.rows_per_scale != a.map_T) return VTX_ERR_SHAPE;
   if (3 * a.map_T < 126) return VTX_ERR_SHAPE;                      // TileRowMap: a 128-row tile spans at most four samples
   if ((uint64_t)a.M * (uint64_t)a.map_T >= 0x100000000ull) return VTX_ERR_SHAPE;   // row / T by __umulhi is exact below 2^32 / T (as the mapped LayerNorm)
   if (a.Mk < a.M && a.resid == nullptr) return VTX_ERR_SHAPE;       // copy-only rows need something to copy
-  if (gemm_pp_ok(a)) return gemm_pp_launch(a, st);
-  if (gemm_astat_ok(a)) return gemm_astat_launch(a, st);
-  return glds_launch_bn<128>(a, st);
+  return VTX_OK;
 }
 
-int gemm_glds_launch(const GemmArgs& a, hipStream_t st) {
-  if (gemm_pp_ok(a)) return gemm_pp_launch(a, st);
-  if (gemm_astat_ok(a)) return gemm_astat_launch(a, st);
-  if (a.N % 128 == 0) return glds_launch_bn<128>(a, st);
-  if (a.N % 96 == 0) return glds_launch_bn<96>(a, st);
-  if (a.N <= 64) return glds_launch_bn<64>(a, st);
-  return glds_launch_bn<128>(a, st);
+// the tiled kernels take whatever gemm_glds_ok admits: column tile by N, tile height by glds_pick_bm, then the pipeline configuration
+void gemm_glds_route(const GemmArgs& a, GemmRoute& r) {
+  r.bn = a.N % 128 == 0 ? 128 : (a.N % 96 == 0 ? 96 : (a.N <= 64 ? 64 : 128));
+  r.bm = glds_pick_bm(a, r.bn);
+  r.family = GEMM_FAM_GLDS;
+  r.bk = 64; r.stages = 2; r.nwn = 2;
+  r.mapped = a.perm != nullptr;
+  if (r.bn != 128) return;
+  if (a.K % 64 != 0) { r.bk = 32; r.stages = 3; return; }
+  // 2 x 4 waves: fwd 3.95 -> 3.78, dgrad 3.66 -> 3.55 ms per step on the Swin stage-2..4 shapes, ViT-S/16 4.64 -> 4.38 /
+  // 4.14 -> 4.07 (the activation epilogues gain most); option GLDS_WAVES = 4 keeps the 2 x 2 variant for comparison
+  if (vtx_opt(VTX_OPT_GLDS_EPI) == 1) { r.family = GEMM_FAM_GLDS_PV; r.nwn = r.bm == 128 ? 2 : 4; return; }
+  if (vtx_opt(VTX_OPT_GLDS_WAVES) != 4) r.nwn = 4;
+}
+
+template <int BM, int BN> static int glds_launch_t(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
+  if constexpr (BN == 128) {
+    // (the row map of stochastic-depth compaction is a compile-time variant: the unmapped kernels carry none of its code)
+    if (r.family == GEMM_FAM_GLDS_PV)
+      return r.mapped ? glds_launch_pv_m<BM, BM == 128 ? 2 : 4, true>(a, st) : glds_launch_pv_m<BM, BM == 128 ? 2 : 4, false>(a, st);
+    if (r.bk == 32) return glds_launch_cfg<BM, BN, 32, 3>(a, st);
+    if (r.nwn == 4) return glds_launch_cfg<BM, BN, 64, 2, 4>(a, st);
+  }
+  return glds_launch_cfg<BM, BN, 64, 2>(a, st);
+}
+template <int BN> static int glds_launch_bn(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
+  return r.bm == 64 ? glds_launch_t<64, BN>(a, r, st) : glds_launch_t<128, BN>(a, r, st);
+}
+
+int gemm_glds_launch(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
+  switch (r.bn) {
+    case 128: return glds_launch_bn<128>(a, r, st);
+    case 96: return glds_launch_bn<96>(a, r, st);
+    case 64: return glds_launch_bn<64>(a, r, st);
+    default: return VTX_ERR_SHAPE;
+  }
+}
+void gemm_glds_label(const GemmRoute& r, char* buf, size_t n) {
+  if (r.family == GEMM_FAM_GLDS_PV) snprintf(buf, n, "gemm_glds_pv_kernel<%d, %d, %s>", r.bm, r.nwn, r.mapped ? "true" : "false");
+  else snprintf(buf, n, "gemm_glds_kernel<%d, %d, %d, %d, %d>", r.bm, r.bn, r.bk, r.stages, r.nwn);
 }

@@ -356,9 +356,6 @@ template <int WMF, bool MAPPED, int ABL = 0, int NF = PP_NF> int pp_launch_k(con
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(PP_NT), smem, st, a, gr);
   return vtx_check_launch();
 }
-template <int WMF, int NF = PP_NF> int pp_launch_m(const GemmArgs& a, hipStream_t st) {
-  return a.perm != nullptr ? pp_launch_k<WMF, true, 0, NF>(a, st) : pp_launch_k<WMF, false, 0, NF>(a, st);
-}
 
 // Tile height: the fewest rounds of one-workgroup-per-CU tiles, then the smallest tiles that still fit that many rounds.
 int pp_pick_wmf(long rows, int ntn, int wmax = 7) {
@@ -380,7 +377,7 @@ int pp_pick_wmf(long rows, int ntn, int wmax = 7) {
 static int pp_nf(int N) { return N % 192 == 0 ? 3 : (N % 256 == 0 ? 4 : (N % 128 == 0 ? 2 : 0)); }
 static int pp_wmax(int nf) { return nf == 4 ? 5 : 7; }
 
-bool gemm_pp_ok(const GemmArgs& a) {
+static bool gemm_pp_ok(const GemmArgs& a) {
   const int mode = vtx_opt(VTX_OPT_GEMM_PP);
   if (mode == 0) return false;
   const int nf = pp_nf(a.N);
@@ -423,24 +420,33 @@ bool gemm_pp_ok(const GemmArgs& a) {
   return true;
 }
 
-int gemm_pp_launch(const GemmArgs& a, hipStream_t st) {
+bool gemm_pp_route(const GemmArgs& a, GemmRoute& r) {
+  if (!gemm_pp_ok(a)) return false;
   const int mode = vtx_opt(VTX_OPT_GEMM_PP);
   const int nf = pp_nf(a.N);
+  const bool forced = mode >= 100 && mode < 1000;                      // forced tile height (tools / tests): 10W -> 32 W rows
+  int w = pp_pick_wmf(a.perm != nullptr ? a.Mk : a.M, a.N / (64 * nf), pp_wmax(nf));
   if (nf != PP_NF) {
-    int w = pp_pick_wmf(a.perm != nullptr ? a.Mk : a.M, a.N / (64 * nf), pp_wmax(nf));
-    if (mode >= 100 && mode < 1000) w = mode % 10 > pp_wmax(nf) ? pp_wmax(nf) : mode % 10;
-    if (nf == 4) return w == 4 ? pp_launch_m<4, 4>(a, st) : pp_launch_m<5, 4>(a, st);
-    switch (w) {
-      case 4: return pp_launch_m<4, 2>(a, st);
-      case 5: return pp_launch_m<5, 2>(a, st);
-      case 6: return pp_launch_m<6, 2>(a, st);
-      case 7: return pp_launch_m<7, 2>(a, st);
-      default: return VTX_ERR_SHAPE;
-    }
+    if (forced) w = mode % 10 > pp_wmax(nf) ? pp_wmax(nf) : mode % 10;
+    if (nf == 4 && w != 4) w = 5;                                      // (256-column tiles: two heights)
+  } else if (forced) {
+    w = mode % 10;
   }
-  int wmf = pp_pick_wmf(a.perm != nullptr ? a.Mk : a.M, a.N / PP_BN);
+  r.family = GEMM_FAM_PP;
+  r.nf = nf;
+  r.wmf = w;
+  r.mapped = a.perm != nullptr;
+  return true;
+}
+
+template <int WMF, int NF = PP_NF> static int pp_launch_m(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
+  return r.mapped ? pp_launch_k<WMF, true, 0, NF>(a, st) : pp_launch_k<WMF, false, 0, NF>(a, st);
+}
+
+int gemm_pp_launch(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
 #ifdef VTX_PP_ABLATE
-  if (mode >= 1000 && a.perm == nullptr) {                             // timing probes: mode = 1000 * ablation bits (WMF 7)
+  const int mode = vtx_opt(VTX_OPT_GEMM_PP);
+  if (r.nf == PP_NF && mode >= 1000 && !r.mapped) {                    // timing probes: mode = 1000 * ablation bits (WMF 7)
     switch (mode / 1000) {
       case 1: return pp_launch_k<7, false, 1>(a, st);
       case 2: return pp_launch_k<7, false, 2>(a, st);
@@ -456,12 +462,25 @@ int gemm_pp_launch(const GemmArgs& a, hipStream_t st) {
     }
   }
 #endif
-  if (mode >= 100 && mode < 1000) wmf = mode % 10;                     // forced tile height (tools / tests): 10W -> 32 W rows
-  switch (wmf) {
-    case 4: return pp_launch_m<4>(a, st);
-    case 5: return pp_launch_m<5>(a, st);
-    case 6: return pp_launch_m<6>(a, st);
-    case 7: return pp_launch_m<7>(a, st);
+  if (r.nf == 4) return r.wmf == 4 ? pp_launch_m<4, 4>(a, r, st) : pp_launch_m<5, 4>(a, r, st);
+  if (r.nf == 2) {
+    switch (r.wmf) {
+      case 4: return pp_launch_m<4, 2>(a, r, st);
+      case 5: return pp_launch_m<5, 2>(a, r, st);
+      case 6: return pp_launch_m<6, 2>(a, r, st);
+      case 7: return pp_launch_m<7, 2>(a, r, st);
+      default: return VTX_ERR_SHAPE;
+    }
+  }
+  switch (r.wmf) {
+    case 4: return pp_launch_m<4>(a, r, st);
+    case 5: return pp_launch_m<5>(a, r, st);
+    case 6: return pp_launch_m<6>(a, r, st);
+    case 7: return pp_launch_m<7>(a, r, st);
     default: return VTX_ERR_SHAPE;
   }
+}
+void gemm_pp_label(const GemmRoute& r, char* buf, size_t n) {
+  if (r.nf == PP_NF) snprintf(buf, n, "gemm_pp_kernel<%d, %s, 0>", r.wmf, r.mapped ? "true" : "false");
+  else snprintf(buf, n, "gemm_ppn_kernel<%d, %s, %d>", r.wmf, r.mapped ? "true" : "false", r.nf);
 }

@@ -358,7 +358,7 @@ static int skinny_chunks(int N, int K) {
   return 0;
 }
 
-bool gemm_skinny_ok(const GemmArgs& a) {
+static bool gemm_skinny_ok(const GemmArgs& a) {
   if (vtx_opt(VTX_OPT_GEMM_SKINNY) == 0 || a.perm != nullptr) return false;
   // (launches whose epilogue READS a vector per output vector -- residual, z of act' -- stay on the tiled kernels unless option
   //  GEMM_SKINNY = 2: with 4 waves per CU the loads are exposed; measured fc2 dgrad 160 -> 215 us, proj forward 44 -> 47 us)
@@ -418,27 +418,40 @@ int vtx_ln_gemm(int dtype, const void* x, const float* gamma, const float* beta,
   return ln_gemm_launch(x, gamma, beta, eps, ln_out, mean, rstd, w, bias, y, M, C, N, (hipStream_t)stream);
 }
 }  // extern "C"
-template <int KS, int ACT, bool VEC> static int skinny_launch_kav(const GemmArgs& a, hipStream_t st) {
-  switch (vtx_opt(VTX_OPT_SKINNY_WAVES)) {
+bool gemm_skinny_route(const GemmArgs& a, GemmRoute& r) {
+  if (!gemm_skinny_ok(a)) return false;
+  r.family = GEMM_FAM_SKINNY;
+  r.nkt = a.K / 32;
+  r.act = a.act;
+  r.resid = a.resid != nullptr || a.act == 2 || a.act == 4;          // (act': z is always read)
+  const int w = vtx_opt(VTX_OPT_SKINNY_WAVES);
+  r.waves = (w == 16 || w == 8) ? w : 4;
+  return true;
+}
+
+template <int KS, int ACT, bool VEC> static int skinny_launch_kav(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
+  switch (r.waves) {
     case 16: return skinny_launch_kavw<KS, ACT, VEC, 16>(a, st);
     case 8: return skinny_launch_kavw<KS, ACT, VEC, 8>(a, st);
     default: return skinny_launch_kavw<KS, ACT, VEC, 4>(a, st);
   }
 }
 
-template <int KS> static int skinny_launch_k(const GemmArgs& a, hipStream_t st) {
-  const bool vec = a.resid != nullptr;
-  switch (a.act) {
-    case 0: return vec ? skinny_launch_kav<KS, 0, true>(a, st) : skinny_launch_kav<KS, 0, false>(a, st);
-    case 1: return vec ? skinny_launch_kav<KS, 1, true>(a, st) : skinny_launch_kav<KS, 1, false>(a, st);
-    case 3: return vec ? skinny_launch_kav<KS, 3, true>(a, st) : skinny_launch_kav<KS, 3, false>(a, st);
-    case 2: return skinny_launch_kav<KS, 2, true>(a, st);           // (act': z is always read)
-    default: return skinny_launch_kav<KS, 4, true>(a, st);
+template <int KS> static int skinny_launch_k(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
+  const bool vec = r.resid != 0;
+  switch (r.act) {
+    case 0: return vec ? skinny_launch_kav<KS, 0, true>(a, r, st) : skinny_launch_kav<KS, 0, false>(a, r, st);
+    case 1: return vec ? skinny_launch_kav<KS, 1, true>(a, r, st) : skinny_launch_kav<KS, 1, false>(a, r, st);
+    case 3: return vec ? skinny_launch_kav<KS, 3, true>(a, r, st) : skinny_launch_kav<KS, 3, false>(a, r, st);
+    case 2: return skinny_launch_kav<KS, 2, true>(a, r, st);
+    default: return skinny_launch_kav<KS, 4, true>(a, r, st);
   }
 }
 
-int gemm_skinny_launch(const GemmArgs& a, hipStream_t st) {
-  if (a.K == 64) return skinny_launch_k<2>(a, st);
-  if (a.K == 96) return skinny_launch_k<3>(a, st);
-  return skinny_launch_k<4>(a, st);
+int gemm_skinny_launch(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
+  if (r.nkt == 2) return skinny_launch_k<2>(a, r, st);
+  if (r.nkt == 3) return skinny_launch_k<3>(a, r, st);
+  return skinny_launch_k<4>(a, r, st);
 }
+// (the name tools and tests know: the k-tiles only)
+void gemm_skinny_label(const GemmRoute& r, char* buf, size_t n) { snprintf(buf, n, "gemm_skinny_kernel<%d>", r.nkt); }

@@ -897,10 +897,38 @@ template <bool MAPPED, bool TG, int J> static int wgrad_wide_launch_cfg(const Wg
   return vtx_check_launch();
 }
 
-// wide: 0 = 128 x 128 tiles | J = 3 .. 6: 128 x 64 J tiles (wgrad_wide_tiles)
+// 8 waves per workgroup: every shape of Swin-S / ViT-S 9-11 % faster than with 4 (stage-2..4 weight gradients 5.20 ->
+// 4.72 ms, ViT-S/16 4.66 -> 4.16 ms per step); 16 waves (one workgroup per CU: 73 registers) 5.6 vs 4.25 ms.
+// option WG_WAVES = 4 keeps the 2 x 2 variant for comparison (it has no row-mapped instantiation)
+// (ring geometries measured in round 2 and removed: 64 tokens x 3 stages, 32 x 3 / 4 / 5 -- all slower than 64 x 2,
+//  profiles/round2_wgrad_ring_variants.txt)
+void wgrad_glds_route(bool mapped, WgradRoute& r) {
+  r = WgradRoute{};
+  r.family = WGRAD_FAM_GLDS;
+  r.waves = vtx_opt(VTX_OPT_WG_WAVES) == 4 ? 4 : 8;
+  r.mapped = mapped && r.waves == 8;
+}
+void wgrad_group_route(int nprob, const int* N, const int* Kin, bool mapped, WgradRoute& r) {
+  int J = 0;
+  const int wt = wgrad_wide_tiles(nprob, N, Kin, &J);
+  if (wt <= 0) return wgrad_glds_route(mapped, r);
+  r = WgradRoute{};
+  r.family = WGRAD_FAM_WIDE;
+  r.wide_j = J; r.tiles = wt;
+  r.tg = J == 6 && (vtx_opt(VTX_OPT_WGRAD_WIDE) & 3) == 2;      // two wave groups half a k-step apart (384-column tiles only)
+  r.mapped = mapped;
+}
+// (the names tools and tests know: the wide kernel by its row map only)
+void wgrad_route_label(const WgradRoute& r, char* buf, size_t n) {
+  if (r.family == WGRAD_FAM_REG) gemm_route_label(r.reg, buf, n);
+  else if (r.family == WGRAD_FAM_WIDE) snprintf(buf, n, "wgrad_wide_kernel<%s>", r.mapped ? "true" : "false");
+  else snprintf(buf, n, "wgrad_glds_kernel<64, 2, %d, %s>", r.waves, r.mapped ? "true" : "false");
+}
+
 int wgrad_glds_group_launch(int nprob, const WgradProbHost* hp, int64_t mtok, int rows_per_scale, float scale_const,
-                            int nz, int kchunk, hipStream_t st, int wide) {
+                            int nz, int kchunk, hipStream_t st, const WgradRoute& r) {
   if (nprob < 1 || nprob > WG_MAXPROB) return VTX_ERR_SHAPE;
+  const int wide = r.family == WGRAD_FAM_WIDE ? r.wide_j : 0;
   WgradArgs a;
   int t0 = 0;
   bool any_scale = false;
@@ -920,34 +948,20 @@ int wgrad_glds_group_launch(int nprob, const WgradProbHost* hp, int64_t mtok, in
   a.nprob = nprob; a.M = (int)mtok; a.rows_per_scale = rows_per_scale > 0 ? rows_per_scale : 1;
   a.scale_const = scale_const; a.kchunk = kchunk; a.nz = nz; a.ntiles = t0;
   if (any_scale && kchunk / a.rows_per_scale + 2 > WG_MAXSAMPLES) return VTX_ERR_SHAPE;
-  // 8 waves per workgroup: every shape of Swin-S / ViT-S 9-11 % faster than with 4 (stage-2..4 weight gradients 5.20 ->
-  // 4.72 ms, ViT-S/16 4.66 -> 4.16 ms per step); 16 waves (one workgroup per CU: 73 registers) 5.6 vs 4.25 ms.
-  // option WG_WAVES = 4 keeps the 2 x 2 variant for comparison
-  if (wide) {
-    bool wmapped = false;
-    for (int i = 0; i < nprob; ++i) wmapped = wmapped || hp[i].perm != nullptr;
-    for (int i = 0; i < nprob; ++i)
-      if (wmapped && hp[i].perm == nullptr) return VTX_ERR_SHAPE;
-    const bool tg = (vtx_opt(VTX_OPT_WGRAD_WIDE) & 3) == 2;     // two wave groups half a k-step apart (384-column tiles only)
-    if (wide == 6) {
-      if (tg) return wmapped ? wgrad_wide_launch_cfg<true, true, 6>(a, st) : wgrad_wide_launch_cfg<false, true, 6>(a, st);
-      return wmapped ? wgrad_wide_launch_cfg<true, false, 6>(a, st) : wgrad_wide_launch_cfg<false, false, 6>(a, st);
-    }
-    if (wide == 5) return wmapped ? wgrad_wide_launch_cfg<true, false, 5>(a, st) : wgrad_wide_launch_cfg<false, false, 5>(a, st);
-    if (wide == 4) return wmapped ? wgrad_wide_launch_cfg<true, false, 4>(a, st) : wgrad_wide_launch_cfg<false, false, 4>(a, st);
-    // (row-mapped problems come from compacted layers, whose C and ff are multiples of 128: a group whose widths also divide by 192
-    //  divides by 384 and has taken J = 6 -- no row-mapped 192-column instantiation)
-    return wmapped ? VTX_ERR_SHAPE : wgrad_wide_launch_cfg<false, false, 3>(a, st);
-  }
-  if (vtx_opt(VTX_OPT_WG_WAVES) == 4) return wgrad_glds_launch_cfg<64, 2, 4>(a, st);
-  // (ring geometries measured in round 2 and removed: 64 tokens x 3 stages, 32 x 3 / 4 / 5 -- all slower than 64 x 2,
-  //  profiles/round2_wgrad_ring_variants.txt)
-  bool mapped = false;
-  for (int i = 0; i < nprob; ++i) mapped = mapped || hp[i].perm != nullptr;
-  if (mapped) {
+  if (r.mapped)
     for (int i = 0; i < nprob; ++i)
       if (hp[i].perm == nullptr) return VTX_ERR_SHAPE;        // all problems of a launch are mapped, or none
-    return wgrad_glds_launch_cfg<64, 2, 8, true>(a, st);
+  if (wide) {
+    if (wide == 6) {
+      if (r.tg) return r.mapped ? wgrad_wide_launch_cfg<true, true, 6>(a, st) : wgrad_wide_launch_cfg<false, true, 6>(a, st);
+      return r.mapped ? wgrad_wide_launch_cfg<true, false, 6>(a, st) : wgrad_wide_launch_cfg<false, false, 6>(a, st);
+    }
+    if (wide == 5) return r.mapped ? wgrad_wide_launch_cfg<true, false, 5>(a, st) : wgrad_wide_launch_cfg<false, false, 5>(a, st);
+    if (wide == 4) return r.mapped ? wgrad_wide_launch_cfg<true, false, 4>(a, st) : wgrad_wide_launch_cfg<false, false, 4>(a, st);
+    // (row-mapped problems come from compacted layers, whose C and ff are multiples of 128: a group whose widths also divide by 192
+    //  divides by 384 and has taken J = 6 -- no row-mapped 192-column instantiation)
+    return r.mapped ? VTX_ERR_SHAPE : wgrad_wide_launch_cfg<false, false, 3>(a, st);
   }
-  return wgrad_glds_launch_cfg<64, 2, 8>(a, st);
+  if (r.waves == 4) return wgrad_glds_launch_cfg<64, 2, 4>(a, st);
+  return r.mapped ? wgrad_glds_launch_cfg<64, 2, 8, true>(a, st) : wgrad_glds_launch_cfg<64, 2, 8>(a, st);
 }

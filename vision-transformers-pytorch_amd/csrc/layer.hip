@@ -74,20 +74,26 @@ int layer_gemm_mapped(const void* A, const void* W, void* Cc, int M, int Mk, int
   a.ksum_out = nullptr; a.perm = perm; a.map_T = T; a.Mk = Mk; a.map_magic = vtx_div_magic(T);
   if (!A || !W || !Cc || !perm) return VTX_ERR_NULL;
   if ((act == 2 || act == 4) && !aux_in) return VTX_ERR_NULL;
-  return gemm_glds_launch_mapped(a, (hipStream_t)st);
+  int rc = gemm_mapped_validate(a);
+  if (rc) return rc;
+  GemmRoute r;
+  rc = gemm_route(a, 0, VTX_BF16, r);
+  return rc ? rc : gemm_route_launch(a, r, 1, (hipStream_t)st);
 }
 
 }  // namespace
 
 extern "C" {
 
-/* sizeof the descriptors (0: VtxLayerFwd, 1: VtxLayerBwd): the bindings check their mirror structures against it */
+/* sizeof the descriptors (0: VtxLayerFwd, 1: VtxLayerBwd, 2 / 3: the VtxSrLayer pair, 4: VtxRoute, 5: VtxGemmQuery): the bindings check their mirror structures against it */
 int vtx_layer_desc_bytes(int which) {
   switch (which) {
     case 0: return (int)sizeof(VtxLayerFwd);
     case 1: return (int)sizeof(VtxLayerBwd);
     case 2: return (int)sizeof(VtxSrLayerFwd);
     case 3: return (int)sizeof(VtxSrLayerBwd);
+    case 4: return (int)sizeof(VtxRoute);
+    case 5: return (int)sizeof(VtxGemmQuery);
     default: return 0;
   }
 }

@@ -96,6 +96,20 @@ class TimerRec(ctypes.Structure):
     _fields_ = [("tag", _I), ("n", _I), ("k", _I), ("flags", _I), ("rows", _L), ("ms", _F)]
 
 
+class Route(ctypes.Structure):
+    """include/vtx.h VtxRoute: the kernel instantiation a launch takes, as the library decides it (vtx_*_route)."""
+    _fields_ = ([(n, _I) for n in ("family", "tile_m", "tile_n", "tile_k", "stages", "waves", "wmf", "nf", "ktiles", "mapped", "act",
+                                   "resid", "aux", "wide_j", "tiles", "reserved")] + [("label", ctypes.c_char * 96)])
+
+
+class GemmQuery(ctypes.Structure):
+    """include/vtx.h VtxGemmQuery."""
+    _fields_ = [(n, _I) for n in ("mode", "dtype", "M", "N", "K", "act", "flags", "Mk", "map_T", "rows_per_scale")]
+
+
+Q_RESID, Q_AUXOUT, Q_AUXIN, Q_MAPPED, Q_BIAS, Q_ROWSCALE, Q_INPLACE = 1, 2, 4, 8, 16, 32, 64      # VTX_Q_*
+
+
 _SIGNATURES = {
     "vtx_layer_fwd": (c_int, [c_void_p, c_void_p]),
     "vtx_layer_bwd": (c_int, [c_void_p, c_void_p, c_void_p]),
@@ -133,6 +147,10 @@ _SIGNATURES = {
                                   c_void_p]),
     "vtx_gemm": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int64,
                          c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "vtx_gemm_route": (c_int, [c_void_p, c_void_p]),
+    "vtx_wgrad_route": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_void_p]),
+    "vtx_wattn_route": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "vtx_gemm_glds_ok": (c_int, [c_int, c_int]),
     "vtx_mlp_fused_ok": (c_int, [c_int, c_int64, c_int, c_int]),
     "vtx_mlp_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                             c_void_p, c_int64, c_int, c_int, c_void_p]),
@@ -339,6 +357,8 @@ def load():
         raise VtxError("libvtx.so layer descriptors do not match the bindings (VtxLayerFwd / VtxLayerBwd): rebuild")
     if lib.vtx_layer_desc_bytes(2) != ctypes.sizeof(SrLayerFwd) or lib.vtx_layer_desc_bytes(3) != ctypes.sizeof(SrLayerBwd):
         raise VtxError("libvtx.so layer descriptors do not match the bindings (VtxSrLayerFwd / VtxSrLayerBwd): rebuild")
+    if lib.vtx_layer_desc_bytes(4) != ctypes.sizeof(Route) or lib.vtx_layer_desc_bytes(5) != ctypes.sizeof(GemmQuery):
+        raise VtxError("libvtx.so route records do not match the bindings (VtxRoute / VtxGemmQuery): rebuild")
     if lib.vtx_jpeg_plan_bytes() != ctypes.sizeof(JpegPlan) or lib.vtx_jpeg_scan_bytes() < ctypes.sizeof(JpegScanHead):
         raise VtxError("libvtx.so JPEG records do not match the bindings (VtxJpegPlan / JsScan): rebuild")
     _lib = lib

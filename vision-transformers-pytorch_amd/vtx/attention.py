@@ -4,6 +4,8 @@
 vtx.ops re-exports every name of this module (``ops.attention_fwd``, ``ops.attn_hd_routes``, ...): callers keep using it.  The module
 imports vtx.ops at its END (either of the two may be imported first) and reads the installed KernelTimer as ``ops._timer`` at call time.
 """
+import ctypes
+
 import torch
 
 from . import _lib, options
@@ -95,22 +97,21 @@ def generic_label(dtype, D, L, swin, bias, mask, drop, bwd):
     return f"attn_{d}_kernel"
 
 
+def _wattn_label(dtype, bwd, masked, nbn, inverse_map):
+    r = _lib.Route()
+    _lib.check(_lib.load().vtx_wattn_route(_lib.BF16 if dtype == torch.bfloat16 else _lib.F32, int(bwd), int(bool(masked)), int(nbn),
+                                           int(bool(inverse_map)), ctypes.byref(r)), "vtx_wattn_route")
+    return r.label.decode()
+
+
 def wattn_fwd_kernel_name(dtype, masked, nbn):
-    """Mirrors wattn_fwd_launch (attention_win.hip): bf16 with >= 4 096 (image, window) problems per head takes the four-wave kernel
-    (option WATTN_FWD4: 1 | 2 always | 0 never)."""
-    m = "true" if masked else "false"
-    f4 = options.get("WATTN_FWD4")
-    if dtype == torch.bfloat16 and (f4 >= 2 or (f4 == 1 and nbn >= 4096)):
-        return f"wattn_fwd4_kernel<{m}>"
-    return f"wattn_fwd_kernel<{'__bf16' if dtype == torch.bfloat16 else 'float'}, {m}>"
+    """Kernel of a window-attention forward over ``nbn`` (image, window) problems per head, as wattn_route (attention_win.hip) decides it."""
+    return _wattn_label(dtype, False, masked, nbn, False)
 
 
 def wattn_bwd_kernel_name(dtype, masked, inverse_map=True):
-    """Mirrors wattn_bwd_launch (attention_win.hip): bf16 with the inverse pos map takes the four-wave kernel."""
-    m = "true" if masked else "false"
-    if dtype == torch.bfloat16 and inverse_map and options.get("WATTN_BWD4"):
-        return f"wattn_bwd4_kernel<{m}>"
-    return f"wattn_bwd_kernel<{'__bf16' if dtype == torch.bfloat16 else 'float'}, {m}>"
+    """Kernel of a window-attention backward (``inverse_map``: the call passes the inverse pos map), as wattn_route decides it."""
+    return _wattn_label(dtype, True, masked, 1, inverse_map)
 
 
 # ------------------------------------------------------------------------------- the launch

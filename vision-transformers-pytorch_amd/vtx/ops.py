@@ -254,7 +254,10 @@ def _describe_timer_rec(r):
     mapped = "true" if fl & 8 else "false"
     D = fl >> 8
     if r.tag == 2:                                                      # GEMM: C[rows, n] over k
-        name = gemm_kernel_name(dt, n, 0, K=k, M=rows, mapped=bool(fl & 8), vec=bool(fl & 5))
+        # (flag bits 0..3 are the query's; a record carries neither the activation nor the bias: act' where z is read, an activation where
+        #  it is saved, and the bias assumed present)
+        act = ACT_DSILU if fl & 4 else (ACT_SILU if fl & 2 else ACT_NONE)
+        name = gemm_route(dt, n, k, rows, act=act, flags=(fl & 15) | _lib.Q_BIAS).label.decode()
         nb = es * (rows * k + n * k + rows * n * (1 + bool(fl & 1) + bool(fl & 2) + bool(fl & 4)))
         return name, 2.0 * rows * n * k, float(nb), r.ms
     if r.tag == 1:
@@ -323,102 +326,83 @@ def _describe_timer_rec(r):
     return f"vtx_layer launch (tag {r.tag})", 0.0, 0.0, r.ms
 
 
-def skinny_ok(N, K, M, vec=False):
-    """Mirrors gemm_skinny_ok (gemm_skinny.hip): the weight-resident streaming kernel (contiguous operands assumed);
-    ``vec``: the epilogue reads a residual or z (those launches stay on the tiled kernels unless GEMM_SKINNY = 2)."""
-    opt = options.get("GEMM_SKINNY")
-    fits = any(N % (32 * nc) == 0 and (N // nc) * (K + 8) * 2 + (N // nc) * 4 <= 150 * 1024 for nc in (1, 2, 4))
-    return bool(opt) and (not vec or opt == 2) and K in (64, 96, 128) and N >= 32 and M >= 32768 and fits
-
-
-def glds_ok(N, K):
-    """Shapes the LDS-DMA GEMM takes (mirrors gemm_glds_ok in gemm_glds.hip)."""
-    return K % 64 == 0 or (K % 32 == 0 and N % 128 == 0)
-
-
 def cu_count():
     """Compute units of the current device as the library's dispatch heuristics see them (vtx_cu_count)."""
     return _lib.load().vtx_cu_count()
 
 
-
-def astat_ok(N, K, M, bias=True, plain=True):
-    """Mirrors gemm_astat_ok (gemm_astat.hip) for contiguous bf16 operands: the A-stationary persistent kernel takes C[M, N] over
-    192 <= K <= 384 once a launch has two 128 x 128 tiles per CU (M: the rows a mapped launch computes); N % 128 == 64 (a ragged last
-    column tile) only for ``plain`` launches: no residual / activation / saved z / row map."""
-    mode = options.get("GEMM_ASTAT")
-    if not mode or K % 64 or K < 192 or K > 384 or N % 64 or N < 256 or (N > 1536 and bias) or M <= 0 or (N % 128 and not plain):
-        return False
-    return mode == 2 or 4 * ((M + 127) // 128) * ((N + 127) // 128) >= (5 if mode == 3 else 8) * cu_count()
+# ------------------------------------------------------------------------------- which kernel a launch takes: the library decides, these ask
+def _dtc(dtype):
+    return BF16 if dtype == torch.bfloat16 else F32
 
 
-def pp_nf(N):
-    """16-column accumulator tiles per wave of the two-group GEMM = tile width / 64 (mirrors pp_nf, csrc/gemm_pp.hip); 0: not its shape."""
-    return 3 if N % 192 == 0 else (4 if N % 256 == 0 else (2 if N % 128 == 0 else 0))
+def gemm_route(dtype, N, K, M, mode=0, act=0, bias=True, resid=False, aux_out=False, aux_in=False, rowscale=False, inplace=False,
+               mapped=False, Mk=0, map_T=0, rows_per_scale=1, flags=None):
+    """The kernel instantiation vtx_gemm launches for C[M, N] over K with these epilogue operands, under the current options (vtx_gemm_route:
+    the decision the launcher itself reads) -> _lib.Route (``.label``: the name rocprofv3 prints, ``.family``, tile numbers).  ``mode`` 2:
+    the register-staged weight gradient.  ``mapped``: the row-mapped launch of a compacted branch (``Mk`` rows computed, ``map_T`` rows per
+    sample; 0: unknown).  ``flags``: the _lib.Q_* bits given directly (a timer record's)."""
+    if flags is None:
+        flags = ((_lib.Q_RESID if resid else 0) | (_lib.Q_AUXOUT if aux_out else 0) | (_lib.Q_AUXIN if aux_in else 0) |
+                 (_lib.Q_MAPPED if mapped else 0) | (_lib.Q_BIAS if bias else 0) | (_lib.Q_ROWSCALE if rowscale else 0) |
+                 (_lib.Q_INPLACE if inplace else 0))
+    q = _lib.GemmQuery(mode=mode, dtype=_dtc(dtype), M=int(M), N=int(N), K=int(K), act=int(act), flags=int(flags), Mk=int(Mk or M),
+                       map_T=int(map_T), rows_per_scale=int(rows_per_scale))
+    r = _lib.Route()
+    check(_lib.load().vtx_gemm_route(ctypes.byref(q), ctypes.byref(r)), "vtx_gemm_route")
+    return r
 
 
-def pp_wmf(M, N):
-    """Tile height (in 32-row units) the two-group GEMM picks (mirrors pp_pick_wmf, csrc/gemm_pp.hip)."""
-    nf = pp_nf(N)
-    cus, ntn = cu_count(), N // (64 * nf)
-    wmax = 5 if nf == 4 else 7
-    best, cost = wmax, None
-    for w in range(wmax, 3, -1):
-        tiles = (M + 32 * w - 1) // (32 * w) * ntn
-        c = ((tiles + cus - 1) // cus) * (w + 2)
-        if cost is None or c < cost:
-            best, cost = w, c
-    return best
+def wgrad_route(dtype, pairs, M=1, group=False, mapped=False, rowscale=False, rows_per_scale=1, scale_const=0.0):
+    """The kernel a weight gradient over M tokens takes (vtx_wgrad_route) -> _lib.Route: ``pairs`` = [(N, Kin), ...]; ``group``: the grouped
+    launch (vtx_wgrad_group), else the single vtx_wgrad of pairs[0] (family 3: the register-staged kernel)."""
+    n = len(pairs)
+    Ns, Ks = (ctypes.c_int * n)(*[int(a) for a, _ in pairs]), (ctypes.c_int * n)(*[int(b) for _, b in pairs])
+    r = _lib.Route()
+    check(_lib.load().vtx_wgrad_route(_dtc(dtype), n, Ns, Ks, int(M), (1 if group else 0) | (2 if rowscale else 0) | (4 if mapped else 0),
+                                      int(rows_per_scale), float(scale_const), ctypes.byref(r)), "vtx_wgrad_route")
+    return r
+
+
+def glds_ok(N, K):
+    """Shapes the LDS-DMA GEMM takes (vtx_gemm_glds_ok): a dgrad over them runs on the transposed weight copy."""
+    return bool(_lib.load().vtx_gemm_glds_ok(int(N), int(K)))
+
+
+_PP_K, _PP_M = 1152, 1 << 15     # where only N is asked about: a long contraction over rows that fill the chip
+
+
+def _pp_route(N, K, M):
+    """Route of the plain bf16 forward GEMM C[M, N] over K where it is the two-group kernel's (gemm_pp.hip), else None (a shape the
+    library refuses included)."""
+    try:
+        r = gemm_route(torch.bfloat16, N, K, M)
+    except VtxError:
+        return None
+    return r if r.family == 2 else None
 
 
 def pp_ok(N, K, M):
-    """Mirrors gemm_pp_ok (csrc/gemm_pp.hip) for contiguous bf16 operands: the two-group kernel takes the long contractions
-    (K >= 1152, or K >= 768 with N <= 384, or K >= 384 with N = 192) of N % 192 == 0 layers once a launch nearly fills a round (M: the rows it computes)."""
-    mode = options.get("GEMM_PP")
-    nf = pp_nf(N)
-    if not mode or not nf or K % 64 or M <= 0:
-        return False
-    if mode >= 2:
-        return True
-    if nf != 3:                      # 128-column tiles from K = 1024 up (PVT-Small stage 2); 256-column tiles only under GEMM_PP = 2
-        return nf == 2 and K >= 1024 and 4 * ((M + 127) // 128) * (N // 128) >= 3 * cu_count()
-    return (K >= 1152 or (K >= 768 and N <= 384) or (K >= 384 and N == 192)) and 4 * ((M + 127) // 128) * (N // 192) >= 3 * cu_count()
+    """True where a plain bf16 forward GEMM C[M, N] over K takes the two-group kernel."""
+    return _pp_route(N, K, M) is not None
+
+
+def pp_nf(N, K=_PP_K, M=_PP_M):
+    """16-column accumulator tiles per wave of the two-group GEMM = tile width / 64, for N columns; 0: the kernel does not take them."""
+    r = _pp_route(N, K, M)
+    return r.nf if r else 0
+
+
+def pp_wmf(M, N, K=_PP_K):
+    """Tile height (in 32-row units) the two-group GEMM runs C[M, N] with; 0: the kernel does not take the launch."""
+    r = _pp_route(N, K, M)
+    return r.wmf if r else 0
 
 
 def gemm_kernel_name(dtype, N, mode, out_f32=False, K=0, M=0, mapped=False, vec=False, bias=True):
-    """Name of the kernel instantiation vtx_gemm / vtx_wgrad picks (mirrors gemm.hip / gemm_glds.hip); ``mapped``: the
-    row-mapped variant of a compacted branch (M = the rows it computes)."""
-    t = "__bf16" if dtype == torch.bfloat16 else "float"
-    to = "float" if out_f32 else t
-    bn = 128 if N % 128 == 0 else (96 if N % 96 == 0 else (64 if N <= 64 else 128))
-    if dtype == torch.bfloat16 and mode == 0 and skinny_ok(N, K, M, vec) and not mapped:
-        return f"gemm_skinny_kernel<{K // 32}>"
-    if dtype == torch.bfloat16 and mode == 0 and K > 0 and glds_ok(N, K) and pp_ok(N, K, M):
-        mode_ = options.get("GEMM_PP")
-        nf = pp_nf(N)
-        w = min(mode_ % 10, 5 if nf == 4 else 7) if 100 <= mode_ < 1000 else pp_wmf(M, N)
-        if nf != 3:
-            return f"gemm_ppn_kernel<{w}, {'true' if mapped else 'false'}, {nf}>"
-        return f"gemm_pp_kernel<{w}, {'true' if mapped else 'false'}, 0>"
-    if dtype == torch.bfloat16 and mode == 0 and astat_ok(N, K, M, bias, plain=not vec and not mapped):
-        return f"gemm_astat_kernel<{K // 64}, {'true' if mapped else 'false'}, ...>"
-    if dtype == torch.bfloat16 and mode == 0 and K > 0 and glds_ok(N, K):
-        force = options.get("GLDS_BM")                                     # mirrors glds_pick_bm in gemm_glds.hip
-        if force in (64, 128):
-            bm = force
-        elif bn != 128 or K % 64 != 0:
-            bm = 64
-        else:
-            t128 = ((N + 127) // 128) * ((M + 127) // 128)
-            bm = 128 if (t128 >= 800 or 384 < t128 <= 512) else 64
-        if K % 64 != 0:
-            return f"gemm_glds_kernel<{bm}, {bn}, 32, 3, 2>"
-        if bn == 128 and options.get("GLDS_EPI") == 1:                     # mirrors glds_launch_t: wave-private epilogue
-            return f"gemm_glds_pv_kernel<{bm}, {2 if bm == 128 else 4}, {'true' if mapped else 'false'}>"
-        nwn = 4 if (bn == 128 and options.get("GLDS_WAVES") != 4) else 2
-        return f"gemm_glds_kernel<{bm}, {bn}, 64, 2, {nwn}>"
-    ta, tb = {0: ("false", "false"), 1: ("false", "true"), 2: ("true", "true")}[mode]
-    return f"gemm_kernel<{t}, {to}, 128, {bn}, {ta}, {tb}>"
+    """Name of the kernel instantiation vtx_gemm picks, as the library tells it; ``vec``: the epilogue adds a residual; ``mapped``: the
+    row-mapped variant of a compacted branch (M = the rows it computes); ``out_f32``: the register-staged weight gradient."""
+    return gemm_route(dtype, N, K, M, mode=2 if out_f32 else mode, bias=bias, resid=vec, mapped=mapped).label.decode()
 
 
 # ------------------------------------------------------------------------------- GEMM family
@@ -447,9 +431,10 @@ def gemm(a, w, mode=0, bias=None, resid=None, rowscale=None, rows_per_scale=1, a
     if _timer is not None:
         es = a.element_size()
         nb = es * (M * K + N * K + M * N * (1 + (resid is not None) + bool(want_aux) + (aux_in is not None)))
-        ev = _timer.bracket(gemm_kernel_name(a.dtype, N, mode, K=K, M=M, vec=resid is not None or act in (ACT_DSILU, ACT_DGELU),
-                                             bias=bias is not None),
-                            2.0 * M * N * K, float(nb))
+        route = gemm_route(a.dtype, N, K, M, mode=mode, act=act, bias=bias is not None, resid=resid is not None, aux_out=bool(want_aux),
+                           aux_in=aux_in is not None, rowscale=rowscale is not None, inplace=out is not None and out is resid,
+                           rows_per_scale=rows_per_scale)
+        ev = _timer.bracket(route.label.decode(), 2.0 * M * N * K, float(nb))
     if ev:
         ev[0].record()
     check(lib.vtx_gemm(mode, _dt(a), _p(a), _p(w), _p(c), M, N, K, K, w.shape[1], N, _p(bias), _p(resid),
@@ -460,43 +445,28 @@ def gemm(a, w, mode=0, bias=None, resid=None, rowscale=None, rows_per_scale=1, a
 
 
 def wgrad_wide_tiles(pairs, want_j=False):
-    """128 x 64 J tiles (J = 6 .. 3, the widest whose width divides every Kin) of a grouped weight gradient [(N, Kin), ...], or 0 when
-    the group stays on 128 x 128 tiles (mirrors wgrad_wide_tiles, csrc/gemm_wgrad_glds.hip).  ``want_j``: (tiles, J)."""
-    on = options.get("WGRAD_WIDE")
-    r4 = bool(on & 4)                  # the round-4 rule: whole 128 x 384 tiles only
-    cus = cu_count()
-    fill = ((on >> 4) & 255) or 85
-    all384 = not r4 and all(k % 384 == 0 for _, k in pairs)      # 256-column tiles as the fallback of under-filled 384-column groups (C = 768)
-    for J in ((6,) if r4 else (6, 5, 4, 3)) if on else ():
-        if J == 4 and not (on & 8) and not all384:
-            continue
-        need = 75 if (J == 4 and not (on & 8) and fill > 75) else fill
-        kw = 64 * J
-        if any(k % kw or n % 8 or n < 64 or (r4 and n % 128) for n, k in pairs):
-            continue
-        tiles = sum(((n + 127) // 128) * (k // kw) for n, k in pairs)
-        if 1 <= tiles <= cus and 100 * ((cus // tiles) * tiles) >= need * cus:
-            return (tiles, J) if want_j else tiles
-    return (0, 0) if want_j else 0
+    """128 x 64 J tiles (J = 6 .. 3) of a grouped weight gradient [(N, Kin), ...], or 0 when the group stays on 128 x 128 tiles, as the
+    library decides (wgrad_wide_tiles, csrc/gemm_wgrad_glds.hip).  ``want_j``: (tiles, J)."""
+    r = wgrad_route(torch.bfloat16, pairs, group=True)
+    return (r.tiles, r.wide_j) if want_j else r.tiles
 
 
 def wgrad_group_kernel_name(pairs, mapped="false"):
-    if wgrad_wide_tiles(pairs):
-        return f"wgrad_wide_kernel<{mapped}>"
-    return f"wgrad_glds_kernel<64, 2, {4 if options.get('WG_WAVES') == 4 else 8}, {mapped}>"
-
-
-def wgrad_kernel_name(dtype, N, Kin, glds):
-    if glds:
-        return f"wgrad_glds_kernel<64, 2, {4 if options.get('WG_WAVES') == 4 else 8}, false>"
-    t = "__bf16" if dtype == torch.bfloat16 else "float"
-    bn = 128 if Kin % 128 == 0 else (96 if Kin % 96 == 0 else (64 if Kin <= 64 else 128))
-    return f"gemm_kernel<{t}, float, 128, {bn}, true, true>"
+    return wgrad_route(torch.bfloat16, pairs, group=True, mapped=mapped in (True, "true")).label.decode()
 
 
 def _wgrad_glds_shape(dtype, N, Kin, rowscale, scale_const):
-    return (dtype == torch.bfloat16 and options.get("WGRAD_GLDS") and N % 8 == 0 and Kin % 8 == 0 and N >= 64 and
-            Kin >= 64 and (rowscale is None or scale_const > 0))
+    """True where a single weight gradient dW[N, Kin] takes the LDS-DMA kernel by dtype, shape and row scale (``rowscale``: one is
+    present), as the library decides it for a contraction short enough for the kernel's sample table."""
+    return wgrad_route(dtype, [(N, Kin)], rowscale=rowscale is not None, scale_const=scale_const).family == 1
+
+
+def wgrad_kernel_name(dtype, N, Kin, glds):
+    """Name of a single weight gradient's kernel; ``glds``: the launch took the LDS-DMA path (wgrad_route(...).family tells), else the
+    register-staged kernel."""
+    if glds:
+        return wgrad_route(dtype, [(N, Kin)]).label.decode()
+    return gemm_route(dtype, Kin, 1, N, mode=2).label.decode()
 
 
 def wgrad(dy, x, want_bias=True, rowscale=None, rows_per_scale=1, scale_const=0.0, out=None):
@@ -512,9 +482,9 @@ def wgrad(dy, x, want_bias=True, rowscale=None, rows_per_scale=1, scale_const=0.
     db = torch.empty(N, dtype=torch.float32, device=x.device) if want_bias else None
     wsb = lib.vtx_wgrad_workspace(M, N, Kin)
     ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
-    glds = _wgrad_glds_shape(x.dtype, N, Kin, rowscale, scale_const)
-    with _timed(wgrad_kernel_name(x.dtype, N, Kin, glds) + " (+split-K reduce)", 2.0 * M * N * Kin,
-                x.element_size() * M * (N + Kin) + 4.0 * N * Kin):
+    name = "" if _timer is None else wgrad_route(x.dtype, [(N, Kin)], M, rowscale=rowscale is not None, rows_per_scale=rows_per_scale,
+                                                  scale_const=scale_const).label.decode()
+    with _timed(name + " (+split-K reduce)", 2.0 * M * N * Kin, x.element_size() * M * (N + Kin) + 4.0 * N * Kin):
         check(lib.vtx_wgrad(_dt(x), _p(dy), _p(x), _p(dW), _p(db), M, N, Kin, N, Kin, _p(rowscale),
                             int(rows_per_scale), float(scale_const), _p(ws), wsb, _stream()),
               "vtx_wgrad")
@@ -523,7 +493,7 @@ def wgrad(dy, x, want_bias=True, rowscale=None, rows_per_scale=1, scale_const=0.
 
 def wgrad_group_ok(jobs, rows_per_scale=1, scale_const=0.0):
     """True when ``jobs`` = [(dy, x, want_bias, rowscale), ...] can run as ONE grouped LDS-DMA weight-gradient launch
-    (bf16, same token count, every shape eligible; mirrors vtx_wgrad_group_ok)."""
+    (bf16, same token count, every shape eligible; vtx_wgrad_group_ok decides)."""
     lib = _lib.load()
     n = len(jobs)
     if n < 1 or n > lib.vtx_wgrad_group_max():
@@ -601,7 +571,7 @@ def wgrad_group(jobs, rows_per_scale=1, scale_const=0.0, outs=None, colparts=Non
     cvp = lambda ts: (ctypes.c_void_p * max(nc, 1))(*[None if t is None else t.data_ptr() for t in ts]) if nc else None
     cia = lambda xs: (ctypes.c_int * max(nc, 1))(*xs) if nc else None
     cp = colparts or []
-    with _timed(wgrad_group_kernel_name(list(zip(Nl, Kl))) + (" (+split-K and column reduce)" if nc else " (+split-K reduce)"),
+    with _timed(("" if _timer is None else wgrad_group_kernel_name(list(zip(Nl, Kl)))) + (" (+split-K and column reduce)" if nc else " (+split-K reduce)"),
                 flops, nbytes + sum(4.0 * p.nb * p.ld for p in cp)):
         check(lib.vtx_wgrad_group(BF16, n, vp([j[0] for j in jobs]), vp([j[1] for j in jobs]), vp(dWs), vp(dbs), Ns, Ks,
                                   lds, ldx, vp([j[3] for j in jobs]), int(rows_per_scale), float(scale_const), M, _p(ws),
