@@ -1047,6 +1047,51 @@ int vtx_attn_map_stats(const void* q, const void* k, int64_t ldq, int64_t ldkv, 
 int vtx_attn_map_meter(const float* stats, double* meter, int layer, int B, int nH, int Lq, int n_prefix, void* stream);
 int vtx_attn_mass_mask(const float* maps, uint8_t* mask, int n_maps, int n, float keep, void* stream);
 
+/* ---- Attention maps and statistics for window and halo attention (csrc/attention_maps.hip, template flag WX): what
+ * vtx_attn_map_rows / vtx_attn_map_stats give for global attention, for the layers of Swin, the Twins locally-grouped half and
+ * Halo (reference models/swin_transformer.py:103-160, where `attn` is an ordinary tensor).  The entries above keep their bits.
+ *
+ * Operands exactly as vtx_attn_hdw_fwd takes them.  win > 0: B images, q / k the packed projection of the (H, W) map in map
+ * order; token t of window n of image b is found by the rolled address (shift != 0: the roll by -win / 2); Lq == Lk == win * win;
+ * problems = B * nW.  win == 0: B problems of plain rows (the gathered q | kv pair of halo attention, or a packed projection);
+ * H, W, shift are ignored.  bias fp32 [nH][Lq][Lk] or NULL; mask uint8 [nW][Lq][Lk] or NULL (nonzero: the cell is excluded;
+ * win > 0 only).  Precondition, as in vtx_attn_hdw_fwd: every query row keeps at least one unmasked key; a key block that is
+ * fully masked for a query is fine (the maximum is final before any exponential is taken: no -inf - -inf can appear).
+ *
+ * Scores: a = acc * scale as above (the rounded product); with a bias s = a + bias[h][i][j], a separate fp32 add that is never
+ * contracted with the product; without a bias s = a.  A masked cell and a key >= Lk are excluded: never in the maximum, e = 0
+ * exactly, nothing added to any sum (the entropy term e * s is skipped, not formed).  Passes, lane order and butterfly as above.
+ *
+ * vtx_attn_mapw_rows: p fp32 [problems, nH, nrows, Lk] (a masked cell exactly 0.f), lse fp32 [problems, nH, nrows].
+ * vtx_attn_mapw_stats: stats fp32 [problems, nH, Lq, 5] in the (problem, head, query) order of vtx_attn_hdw_fwd's lse:
+ *     [0] lse = m + __logf(l)                                   bit-equal to the lse of vtx_attn_mapw_rows for that row
+ *     [1] entropy = lse - (sum over unmasked j of e_j s_j) / l
+ *     [2] smax = m                                              the largest score that enters the softmax: bias included, masked
+ *                                                               keys excluded; exact as a maximum
+ *     [3] self = e_self / l                                     the mass on the query's own token
+ *     [4] dist = (sum_j e_j |pos_i - pos_j|) / l                in token units; |.| is v_sqrt_f32 of the exact integer dy^2 + dx^2
+ *   Window mode: token t sits at (t / win, t % win) of its window, queries and keys alike; self is key j == i; gq, gk ignored
+ *   (pairs the shifted partition brings together across the map edge are masked, so window coordinates are true distances for
+ *   every cell that counts).  Halo mode (win == 0): query t sits at (off + t / gq, off + t % gq) of the key grid of width gk,
+ *   off = (gk - gq) / 2; key j at (j / gk, j % gk); self is the key at the query's own position; gq = gk = 0 switches self and
+ *   dist off (0 is stored).  Slot 3 sits where the prefix mass sits: vtx_attn_map_meter with n_prefix = 0 sums
+ *   [queries, sum entropy, sum self, sum dist, queries, max smax] from this tensor.
+ * With win == 0, bias == NULL, mask == NULL and gq = gk = 0, p, lse and slots 0..2 are bit-equal to vtx_attn_map_rows /
+ * vtx_attn_map_stats on the same operands.  A row's outputs are the same bits however the images are cut into calls and however
+ * row0 / nrows cut the rows.  No floating-point atomics.
+ *
+ * Errors, all before any launch, with the codes of the vtx_attn_hdw and vtx_attn_map entries: VTX_ERR_NULL (q, k or an output),
+ * VTX_ERR_DTYPE, VTX_ERR_SHAPE (B, Lq, Lk, nH or nrows < 1; D outside the multiples of 8 in 8..128; row0 < 0 or row0 + nrows >
+ * Lq; a stride below nH * D; win < 0; H or W not a positive multiple of win; Lq != win * win or Lk != Lq with win > 0; a mask with
+ * win == 0; in halo mode with gq, gk not both 0: gq * gq != Lq, gk * gk != Lk, gk < gq or gk - gq odd; problems * Lq >= 2^31 - 1;
+ * nH * Lq * Lk >= 2^31 - 1), VTX_ERR_ALIGN (a stride that is not a multiple of 8; q or k off 16 bytes; an fp32 pointer off 4). */
+int vtx_attn_mapw_rows(const void* q, const void* k, int64_t ldq, int64_t ldkv, float* p, float* lse, const float* bias,
+                       const uint8_t* mask, int B, int Lq, int Lk, int nH, int D, int H, int W, int win, int shift, int row0,
+                       int nrows, int dtype, void* stream);
+int vtx_attn_mapw_stats(const void* q, const void* k, int64_t ldq, int64_t ldkv, float* stats, const float* bias,
+                        const uint8_t* mask, int B, int Lq, int Lk, int nH, int D, int H, int W, int win, int shift, int gq, int gk,
+                        int dtype, void* stream);
+
 /* ---- Multi-tensor weight cast (csrc/cast.hip): all fp32 Linear / Conv weights of a model -> bf16, plain [out][in]
  * and transposed [in][out], in one launch per forward.  This is the per-call weight cast of the reference's bf16
  * autocast (torch.cuda.amp.autocast around model(input), train.py:273-274) done once for the whole model.

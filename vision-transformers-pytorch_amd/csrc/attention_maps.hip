@@ -6,7 +6,8 @@
 // Operands as vtx_attn_hd_fwd (csrc/attention_hd.hip): q [B * Lq, nH * D] with row stride ldq, k [B * Lk, nH * D] with row stride
 // ldkv -- the packed QKV projection (ldq = ldkv = 3 nH D) or the q | kv pair of PVT / Twins -- bf16 or fp32, D any multiple of 8 in
 // 8..128 (templated on the padded width DP in {32, 64, 96, 128}; the PADDING RULE of attention_hd.hip holds: a vector at d0 >= D is a
-// zero operand whose memory is never touched).  No bias, no mask, no windows.
+// zero operand whose memory is never touched).  No bias, no mask, no windows in vtx_attn_map_*; window and halo attention (Swin, the
+// Twins locally-grouped half, Halo) take the same kernels through vtx_attn_mapw_* (WINDOW AND HALO ATTENTION, below).
 //
 // SCORES.  s(q, key) = acc * scale with acc the MFMA chain of hdattn_fwd_kernel -- one v_mfma_f32_16x16x32_bf16 per 32 columns in
 // bf16, eight v_mfma_f32_16x16x4_f32 per 32 columns (the exact fmaf chain) in fp32, fp32 accumulation -- and scale the fp32
@@ -48,9 +49,32 @@
 // map keeps nothing.  DINO's script divides the values by their total before the running sum and compares with 1 - keep; this
 // kernel does not divide (one rounding per element less, and an all-zero map has no 0 / 0): the only difference.
 //
+// WINDOW AND HALO ATTENTION (vtx_attn_mapw_rows / vtx_attn_mapw_stats; template flag WX, every addition behind `if constexpr (WX)`: the
+// instantiations above are what they were).  Operands as vtx_attn_hdw_fwd: with win > 0, B images whose packed projection lies in map
+// order (H, W); token t of window n of image b is found by the rolled address (am_row = the rule of hd_row), Lq = Lk = win * win,
+// problems = B * nW; with win == 0, B problems of plain rows (the gathered q | kv pair of halo attention).  bias fp32 [nH][Lq][Lk] or
+// null; mask bytes [nW][Lq][Lk] or null (win > 0 only), nonzero = excluded; every query row keeps at least one unmasked key (the
+// precondition of vtx_attn_hdw_fwd).  Term by term (am_scores_w = the cell rule of hdw_add):
+//   a_j = acc_j * scale            as above: ONE fp32 multiply, the rounded product settled (acc_settle)
+//   s_j = a_j + bias[h][i][j]      with a bias: a SEPARATE fp32 add of the settled product, never one fma with it; the rounded sum is
+//                                  settled again and IS the score.  Without a bias s_j = a_j: the same bits as the entries above.
+//   excluded cells                 a masked cell and a key >= Lk: never in the maximum (-inf there), e_j = 0 EXACTLY because no
+//                                  exponential is formed for it, nothing added to l, es, the self mass or dist: e_j * s_j is skipped,
+//                                  not formed, so 0 * -inf never appears.  p of a masked cell is stored as 0.f.
+//   passes, lanes, butterfly       as above.  The maximum is final before any exponential is taken, so a key block that is fully masked
+//                                  for a query (the rule in shifted windows of more than 64 tokens) needs no -inf - -inf guard: m is
+//                                  finite and s_j - m is only formed for cells that count.
+//   stats [problems, nH, Lq, 5]    lse = m + __logf(l)    entropy = lse - es / l    smax = m (bias included, masked keys excluded)
+//                                  self = e_self / l      dist = ed / l, ed += e_j * v_sqrt_f32((float)(dy^2 + dx^2))
+//       window mode: token t sits at (t / win, t % win) of its window, queries and keys alike; self is key j == i.
+//       halo mode:   query t sits at (off + t / gq, off + t % gq) of the key grid of width gk, off = (gk - gq) / 2; key j at (j / gk,
+//                    j % gk); self is the key at the query's own position.  gq = gk = 0: self and dist store 0.f.
+//   With win == 0 and no bias, mask or grids, p, lse and slots 0..2 are the bits of vtx_attn_map_rows / _stats on the same operands.
+//   Slot 3 sits where the prefix mass sits: vtx_attn_map_meter with n_prefix = 0 sums [queries, entropy, self, dist, queries, max smax].
+//
 // No floating-point atomics anywhere; every sum has a fixed order, so the same inputs give the same bits.
 //
-// Budget (hipcc resource remarks, gfx950, no scratch in any instantiation): DESIGN.md section 7i.
+// Budget (hipcc resource remarks, gfx950, no scratch in any instantiation): DESIGN.md sections 7i and 7j.
 #include "vtx_common.h"
 
 #define AM_KB 64                 // keys per block (4 tiles of 16)
@@ -65,6 +89,33 @@ struct AmGeom {
   int64_t ldq, ldkv;
   float scale;
 };
+
+// ---- the window / halo entries (vtx_attn_mapw_*): the same kernels with WX = true take this geometry instead (as HdwGeom extends
+// HdGeom in attention_hd.hip).  The existing instantiations (WX = false) see none of it: every addition sits behind `if constexpr (WX)`.
+struct AmwGeom : AmGeom {
+  const float* bias;             // fp32 [nH][Lq][Lk] or null
+  const uint8_t* mask;           // [nW][Lq][Lk] or null; nonzero: the cell is excluded.  Problem (image b, window n) reads mask[n]
+  int H, W, win, shift, nWx, nW; // shift = win / 2 or 0; nW = windows per image (1 with win == 0)
+  int gq, gk;                    // stats, win == 0: the query grid gq x gq centred in the key grid gk x gk; 0, 0: self and dist off
+};
+template <bool WX> struct AmG { using type = AmGeom; };
+template <> struct AmG<true> { using type = AmwGeom; };
+
+// row of token t of problem p (row0 = p * L: the plain address) -- the rule of hd_row (attention_hd.hip), restated: with win > 0 token t
+// of window n of image b is a row of the (H, W) map, the roll by -win / 2 folded into the address
+template <bool WX, typename G> __device__ __forceinline__ int64_t am_row(const G& g, int64_t row0, int p, int t) {
+  if constexpr (WX) {
+    if (g.win) {
+      const int b = p / g.nW, n = p - b * g.nW;
+      const int wi = n / g.nWx, wj = n - wi * g.nWx;
+      const int ay = t / g.win, ax = t - ay * g.win;
+      int y = wi * g.win + ay + g.shift; if (y >= g.H) y -= g.H;   // rolled position p holds original (p + win / 2) mod H
+      int x = wj * g.win + ax + g.shift; if (x >= g.W) x -= g.W;
+      return ((int64_t)b * g.H + y) * g.W + x;
+    }
+  }
+  return row0 + t;
+}
 
 template <typename T> __device__ __forceinline__ Vec8<T> am_load(const T* head, int d0, int D, bool valid) {
   const bool in = d0 < D;
@@ -94,16 +145,60 @@ __device__ __forceinline__ void am_scores(f32x4 (&st)[4], const Vec8<T> (&qf)[DS
   }
 }
 
+// (WX) The scores of key block k0 for query token q of problem `prob` (head h, window nwin of its image) under the cell rule of hdw_add
+// (attention_hd.hip), restated: a_j = acc_j * scale exactly as above; with a bias s_j = a_j + bias[h][q][j], a SEPARATE fp32 add (the
+// rounded product is settled first, so the two are never one fma); a cell whose mask byte is nonzero and a key >= Lk are EXCLUDED: -inf
+// in st and a zero bit in the result, bit 4 kt + r = the cell st[kt][r] counts.  Callers test the bit, never the value.
+template <typename T, int DS>
+__device__ __forceinline__ unsigned am_scores_w(f32x4 (&st)[4], const Vec8<T> (&qf)[DS], const T* __restrict__ kb, const AmwGeom& g, int prob,
+                                                int h, int nwin, int q, int k0, int c_, int g_) {
+  const int64_t cells = (int64_t)g.Lq * g.Lk, cell0 = (int64_t)q * g.Lk;
+  const float* brow = g.bias ? g.bias + h * cells + cell0 : nullptr;
+  const uint8_t* mrow = g.mask ? g.mask + nwin * cells + cell0 : nullptr;
+  unsigned live = 0;
+#pragma unroll
+  for (int kt = 0; kt < 4; ++kt) {
+    st[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int key = k0 + kt * 16 + c_;
+    const bool kv = key < g.Lk;
+    const T* kp = kb + am_row<true>(g, (int64_t)prob * g.Lk, prob, kv ? key : 0) * g.ldkv;
+#pragma unroll
+    for (int ds = 0; ds < DS; ++ds) mma16(am_load<T>(kp, ds * 32 + g_ * 8, g.D, kv), qf[ds], st[kt]);   // S^T[key][q = c_]
+    acc_settle(st[kt]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) st[kt][r] = st[kt][r] * g.scale;
+    acc_settle(st[kt]);          // the rounded product, as in am_scores
+    const int kb0 = k0 + kt * 16 + g_ * 4;
+    if (brow) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (kb0 + r < g.Lk) st[kt][r] += brow[kb0 + r];
+      acc_settle(st[kt]);        // the rounded sum IS the score
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int kk = kb0 + r;
+      bool in = kk < g.Lk;
+      if (in && mrow) in = mrow[kk] == 0;
+      if (in) live |= 1u << (kt * 4 + r);
+      else st[kt][r] = -INFINITY;
+    }
+  }
+  return live;
+}
+
 // What every score kernel starts with: the wave's query (row0 + 16 * (4 block + wave) + c), its fragments, pass 1 and pass 2 for l.
-template <typename T, int DS> struct AmRow {
+template <typename T, int DS, bool WX = false> struct AmRow {
+  using G = typename AmG<WX>::type;
   Vec8<T> qf[DS];
   const T* kb;
   int64_t krow0;
   int bh, qi, q, c_, g_;         // qi: index inside the call's rows; q = row0 + qi
+  int prob, head, nwin;          // (WX) b = problem, its head, the window of the problem inside its image
   bool qv;
   float m;
 
-  __device__ __forceinline__ void init(const T* __restrict__ qp, const T* __restrict__ kp, const AmGeom& g) {
+  __device__ __forceinline__ void init(const T* __restrict__ qp, const T* __restrict__ kp, const G& g) {
     bh = blockIdx.x / g.qblocks;
     const int qblk = blockIdx.x - bh * g.qblocks;
     const int b = bh / g.nH, h = bh - b * g.nH;
@@ -112,17 +207,30 @@ template <typename T, int DS> struct AmRow {
     qi = (qblk * 4 + wave) * 16 + c_;
     qv = qi < g.nrows;
     q = g.row0 + (qv ? qi : 0);
-    const T* qb = qp + h * g.D + ((int64_t)b * g.Lq + q) * g.ldq;
+    const T* qb = qp + h * g.D + am_row<WX>(g, (int64_t)b * g.Lq, b, q) * g.ldq;
 #pragma unroll
     for (int ds = 0; ds < DS; ++ds) qf[ds] = am_load<T>(qb, ds * 32 + g_ * 8, g.D, qv);
     kb = kp + h * g.D;
     krow0 = (int64_t)b * g.Lk;
+    prob = b; head = h; nwin = 0;
+    if constexpr (WX) nwin = b % g.nW;
   }
-  __device__ __forceinline__ bool wave_idle(const AmGeom& g) const { return qi - c_ >= g.nrows; }   // wave-uniform; no barrier follows
-  __device__ __forceinline__ void scores(f32x4 (&st)[4], int k0, const AmGeom& g) const {
-    am_scores<T, DS>(st, qf, kb, krow0, g.ldkv, k0, g.Lk, g.D, g.scale, c_, g_);
+  __device__ __forceinline__ bool wave_idle(const G& g) const { return qi - c_ >= g.nrows; }   // wave-uniform; no barrier follows
+  // -> (WX) the bits of the cells that count (am_scores_w); without WX every key < Lk counts and the result is unused
+  __device__ __forceinline__ unsigned scores(f32x4 (&st)[4], int k0, const G& g) const {
+    if constexpr (WX) {
+      return am_scores_w<T, DS>(st, qf, kb, g, prob, head, nwin, q, k0, c_, g_);
+    } else {
+      am_scores<T, DS>(st, qf, kb, krow0, g.ldkv, k0, g.Lk, g.D, g.scale, c_, g_);
+      return 0u;
+    }
   }
-  __device__ __forceinline__ void pass_max(const AmGeom& g) {
+  // does cell st[kt][r] = key kk of the block count?  (WX) excluded cells never enter a sum: no e_j is formed for them
+  __device__ __forceinline__ bool counts(unsigned live, int kt, int r, int kk, const G& g) const {
+    if constexpr (WX) return (live >> (kt * 4 + r)) & 1u;
+    else return kk < g.Lk;
+  }
+  __device__ __forceinline__ void pass_max(const G& g) {
     float mb = -INFINITY;
     for (int k0 = 0; k0 < g.Lk; k0 += AM_KB) {
       f32x4 st[4];
@@ -144,11 +252,11 @@ __device__ __forceinline__ float am_join(float x) {          // the butterfly of
 
 // ------------------------------------------------------------------------------------------------- rows of P
 // grid = B * nH * ceil(nrows / 64) workgroups of 4 waves; p [B, nH, nrows, Lk], lse [B, nH, nrows]
-template <typename T, int DP>
+template <typename T, int DP, bool WX = false>
 __global__ __launch_bounds__(256) void attn_map_rows_kernel(const T* __restrict__ qp, const T* __restrict__ kp, float* __restrict__ p,
-                                                           float* __restrict__ lse, AmGeom g) {
+                                                           float* __restrict__ lse, typename AmG<WX>::type g) {
   constexpr int DS = DP / 32;
-  AmRow<T, DS> row;
+  AmRow<T, DS, WX> row;
   row.init(qp, kp, g);
   if (row.wave_idle(g)) return;
   row.pass_max(g);
@@ -156,26 +264,30 @@ __global__ __launch_bounds__(256) void attn_map_rows_kernel(const T* __restrict_
   float l = 0.f;
   for (int k0 = 0; k0 < g.Lk; k0 += AM_KB) {
     f32x4 st[4];
-    row.scores(st, k0, g);
+    const unsigned live = row.scores(st, k0, g);
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        if (k0 + kt * 16 + row.g_ * 4 + r < g.Lk) l += __expf(st[kt][r] - m);
+        if (row.counts(live, kt, r, k0 + kt * 16 + row.g_ * 4 + r, g)) l += __expf(st[kt][r] - m);
   }
   l = am_join(l);
   const int64_t orow = (int64_t)row.bh * g.nrows + row.qi;
   if (row.qv && row.g_ == 0) lse[orow] = m + __logf(l);
   for (int k0 = 0; k0 < g.Lk; k0 += AM_KB) {
     f32x4 st[4];
-    row.scores(st, k0, g);
+    const unsigned live = row.scores(st, k0, g);
     if (row.qv) {
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int kk = k0 + kt * 16 + row.g_ * 4 + r;
-          if (kk < g.Lk) p[orow * g.Lk + kk] = __expf(st[kt][r] - m) / l;
+          if constexpr (WX) {
+            if (kk < g.Lk) p[orow * g.Lk + kk] = row.counts(live, kt, r, kk, g) ? __expf(st[kt][r] - m) / l : 0.f;   // masked: exactly 0
+          } else {
+            if (kk < g.Lk) p[orow * g.Lk + kk] = __expf(st[kt][r] - m) / l;
+          }
         }
     }
   }
@@ -183,15 +295,70 @@ __global__ __launch_bounds__(256) void attn_map_rows_kernel(const T* __restrict_
 
 // ------------------------------------------------------------------------------------------------- statistics
 // grid = B * nH * ceil(Lq / 64); stats [B, nH, Lq, 5] = lse, entropy, smax, prefix, dist
-template <typename T, int DP>
+template <typename T, int DP, bool WX = false>
 __global__ __launch_bounds__(256) void attn_map_stats_kernel(const T* __restrict__ qp, const T* __restrict__ kp, float* __restrict__ stats,
-                                                            AmGeom g) {
+                                                            typename AmG<WX>::type g) {
   constexpr int DS = DP / 32;
-  AmRow<T, DS> row;
+  AmRow<T, DS, WX> row;
   row.init(qp, kp, g);
   if (row.wave_idle(g)) return;
   row.pass_max(g);
   const float m = row.m;
+  if constexpr (WX) {
+    // window: token t at (t / win, t % win) for queries and keys; halo: query t at (off + t / gq, off + t % gq) of the key grid of width
+    // gk, key j at (j / gk, j % gk); kw == 0: no positions, self and dist store 0
+    const int kw = g.win ? g.win : g.gk, qw = g.win ? g.win : g.gq;
+    const bool on_grid = kw > 0;
+    int qy = 0, qx = 0, self = -1;
+    if (on_grid) {
+      const int off = g.win ? 0 : (g.gk - g.gq) / 2;
+      qy = row.q / qw; qx = row.q - qy * qw;
+      qy += off; qx += off;
+      self = qy * kw + qx;                                            // the key at the query's own position
+    }
+    float l = 0.f, es = 0.f, ep = 0.f, ed = 0.f;
+    for (int k0 = 0; k0 < g.Lk; k0 += AM_KB) {
+      f32x4 st[4];
+      const unsigned live = row.scores(st, k0, g);
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) {
+        const int kb0 = k0 + kt * 16 + row.g_ * 4;
+        int ky = 0, kx = kb0;
+        if (on_grid) { ky = kb0 / kw; kx = kb0 - ky * kw; }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int kk = kb0 + r;
+          if (row.counts(live, kt, r, kk, g)) {                       // an excluded cell forms no e_j and no e_j * s_j (0 * -inf)
+            const float s = st[kt][r];
+            const float e = __expf(s - m);
+            l += e;
+            es += e * s;
+            if (on_grid) {
+              if (kk == self) ep += e;
+              const int dy = ky - qy, dx = kx - qx;
+              ed += e * __builtin_amdgcn_sqrtf((float)(dy * dy + dx * dx));
+            }
+          }
+          if (on_grid && ++kx == kw) { kx = 0; ++ky; }
+        }
+      }
+    }
+    l = am_join(l);
+    es = am_join(es);
+    ep = am_join(ep);
+    ed = am_join(ed);
+    if (row.qv && row.g_ == 0) {
+      const float ls = m + __logf(l);
+      float* out = stats + ((int64_t)row.bh * g.Lq + row.q) * 5;
+      out[0] = ls;
+      out[1] = ls - es / l;
+      out[2] = m;
+      out[3] = on_grid ? ep / l : 0.f;
+      out[4] = on_grid ? ed / l : 0.f;
+    }
+    return;
+  }
+  // ---- WX = false: the statistics of global attention (prefix tokens, one grid shared by queries and keys), as before
   const int np = g.n_prefix, gw = g.gw;
   const bool on_grid = gw > 0 && row.q >= np;                       // this query has a grid position and dist is on
   int qy = 0, qx = 0;
@@ -365,6 +532,43 @@ static int am_geom(AmGeom& g, int B, int Lq, int Lk, int nH, int D, int row0, in
 }
 static bool am_aligned(const void* p, uintptr_t mask) { return ((uintptr_t)p & mask) == 0; }
 
+// ---- the window / halo entries
+template <typename T, int DP> static int amw_rows_t(const void* q, const void* k, float* p, float* lse, int nprob, const AmwGeom& g, hipStream_t st) {
+  hipLaunchKernelGGL((attn_map_rows_kernel<T, DP, true>), dim3((unsigned)(nprob * g.nH * g.qblocks)), dim3(256), 0, st, (const T*)q,
+                     (const T*)k, p, lse, g);
+  return vtx_check_launch();
+}
+template <typename T, int DP> static int amw_stats_t(const void* q, const void* k, float* stats, int nprob, const AmwGeom& g, hipStream_t st) {
+  hipLaunchKernelGGL((attn_map_stats_kernel<T, DP, true>), dim3((unsigned)(nprob * g.nH * g.qblocks)), dim3(256), 0, st, (const T*)q,
+                     (const T*)k, stats, g);
+  return vtx_check_launch();
+}
+// Everything the two window / halo entries refuse, before any launch, with the codes of hdw_geom (attention_hd.hip) and am_geom;
+// nprob = the problems of the call: B with win == 0, B * windows per image with win > 0.
+static int amw_geom(AmwGeom& g, int64_t& nprob, const float* bias, const uint8_t* mask, int B, int Lq, int Lk, int nH, int D, int H, int W,
+                    int win, int shift, int row0, int nrows, int dtype, int64_t ldq, int64_t ldkv) {
+  if (dtype != VTX_BF16 && dtype != VTX_F32) return VTX_ERR_DTYPE;
+  if (B <= 0 || Lq <= 0 || Lk <= 0 || win < 0) return VTX_ERR_SHAPE;
+  nprob = B;
+  if (win > 0) {
+    if (H <= 0 || W <= 0 || H % win || W % win || (int64_t)win * win != Lq || Lq != Lk) return VTX_ERR_SHAPE;
+    nprob = (int64_t)B * (H / win) * (W / win);
+  } else if (mask != nullptr) {
+    return VTX_ERR_SHAPE;                                           // the mask is per window
+  }
+  if (nprob >= 0x7fffffffLL) return VTX_ERR_SHAPE;
+  AmGeom base;
+  int rc = am_geom(base, (int)nprob, Lq, Lk, nH, D, row0, nrows, dtype, ldq, ldkv);
+  if (rc) return rc;
+  if ((int64_t)nH * Lq * Lk >= 0x7fffffffLL) return VTX_ERR_SHAPE;
+  static_cast<AmGeom&>(g) = base;
+  g.bias = bias; g.mask = mask;
+  g.H = H; g.W = W; g.win = win; g.shift = (win && shift) ? win / 2 : 0;
+  g.nWx = win ? W / win : 1; g.nW = win ? (H / win) * (W / win) : 1;
+  g.gq = 0; g.gk = 0;
+  return VTX_OK;
+}
+
 extern "C" {
 
 /* include/vtx.h: vtx_attn_map_rows */
@@ -394,6 +598,37 @@ int vtx_attn_map_stats(const void* q, const void* k, int64_t ldq, int64_t ldkv, 
   g.n_prefix = n_prefix; g.gh = gh; g.gw = gw;
   hipStream_t st = (hipStream_t)stream;
   return AM_DISPATCH(am_stats_t, q, k, stats, B, g, st);
+}
+
+/* include/vtx.h: vtx_attn_mapw_rows */
+int vtx_attn_mapw_rows(const void* q, const void* k, int64_t ldq, int64_t ldkv, float* p, float* lse, const float* bias,
+                       const uint8_t* mask, int B, int Lq, int Lk, int nH, int D, int H, int W, int win, int shift, int row0, int nrows,
+                       int dtype, void* stream) {
+  if (!q || !k || !p || !lse) return VTX_ERR_NULL;
+  AmwGeom g;
+  int64_t nprob;
+  int rc = amw_geom(g, nprob, bias, mask, B, Lq, Lk, nH, D, H, W, win, shift, row0, nrows, dtype, ldq, ldkv);
+  if (rc) return rc;
+  if (!am_aligned(q, 15) || !am_aligned(k, 15) || !am_aligned(p, 3) || !am_aligned(lse, 3) || !am_aligned(bias, 3)) return VTX_ERR_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  return AM_DISPATCH(amw_rows_t, q, k, p, lse, (int)nprob, g, st);
+}
+
+/* include/vtx.h: vtx_attn_mapw_stats */
+int vtx_attn_mapw_stats(const void* q, const void* k, int64_t ldq, int64_t ldkv, float* stats, const float* bias, const uint8_t* mask,
+                        int B, int Lq, int Lk, int nH, int D, int H, int W, int win, int shift, int gq, int gk, int dtype, void* stream) {
+  if (!q || !k || !stats) return VTX_ERR_NULL;
+  AmwGeom g;
+  int64_t nprob;
+  int rc = amw_geom(g, nprob, bias, mask, B, Lq, Lk, nH, D, H, W, win, shift, 0, Lq > 0 ? Lq : 1, dtype, ldq, ldkv);
+  if (rc) return rc;
+  if (win == 0 && (gq != 0 || gk != 0)) {       // the query grid gq x gq sits centred in the key grid gk x gk
+    if (gq <= 0 || gk < gq || (int64_t)gq * gq != Lq || (int64_t)gk * gk != Lk || (gk - gq) % 2) return VTX_ERR_SHAPE;
+    g.gq = gq; g.gk = gk;
+  }
+  if (!am_aligned(q, 15) || !am_aligned(k, 15) || !am_aligned(stats, 3) || !am_aligned(bias, 3)) return VTX_ERR_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  return AM_DISPATCH(amw_stats_t, q, k, stats, (int)nprob, g, st);
 }
 
 /* include/vtx.h: vtx_attn_map_meter */

@@ -14,7 +14,7 @@ Features are NHWC (B, H, W, C) like the reference; roll, window partition and he
 arithmetic inside the attention kernel.
 """
 import math
-from typing import Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 from torch import nn
@@ -180,6 +180,20 @@ class PatchMerge(nn.Module):
         return VF.PatchMergeFn.apply(input.to(T), self.norm.weight, self.norm.bias, self.linear.weight, self.norm.eps)
 
 
+class AttentionTap(NamedTuple):
+    """What SwinTransformer.attention_inputs hands to vtx.attnmap for one layer: ``qkv`` (B, H, W, 3 dim) in map order, ``bias`` fp32
+    [n_head, L, L] (the relative-position table through ``pos``), ``mask`` uint8 [nW, L, L] (the layer's local_mask; None when the
+    layer is not shifted) and the window geometry."""
+    qkv: torch.Tensor
+    bias: torch.Tensor
+    mask: Optional[torch.Tensor]
+    n_head: int
+    dim_head: int
+    map_size: Tuple[int, int]
+    window: int
+    shift: bool
+
+
 def reduce_size(size, reduction):
     return tuple(side // reduction for side in size[:2])
 
@@ -229,6 +243,59 @@ class SwinTransformer(nn.Module):
         layers = [m for stage in self.stages() for m in stage if hasattr(m, "set_drop_path")]
         for layer, rate in zip(layers, stochastic_depth_rates(drop_path, sum(self.depths), endpoint=False)):
             layer.set_drop_path(rate)
+
+    def attention_layers(self):
+        """The transformer layers of all stages in forward order (PatchMerge modules are not counted)."""
+        return [m for stage in self.stages() for m in stage if hasattr(m, "set_drop_path")]
+
+    def attention_inputs(self, input, layers=(-1,)):
+        """What enters the window attention of ``layers`` (indices into ``attention_layers()``, negative from the end), for
+        ``vtx.attnmap``: what a forward hook on the reference's ``attn`` (swin_transformer.py:103-160) is computed from.  Needs
+        ``eval()``, ``torch.no_grad()`` and ONE image tensor on the device (a list of crops is refused).  The forward is
+        ``forward``'s own, piece by piece and untouched; in front of each requested layer its LayerNorm and QKV linear run once
+        more as separate launches (the fused layer call keeps its projection to itself).
+        -> ({layer index: AttentionTap}, the logits ``forward`` returns)."""
+        from vtx.ops import VtxError, table_bias
+        if isinstance(input, (list, tuple)) or not torch.is_tensor(input) or input.dim() != 4:
+            raise VtxError("vtx: attention_inputs takes one (B, 3, H, W) image tensor, not a list of crops")
+        if self.training:
+            raise VtxError("vtx: attention_inputs needs model.eval(): attention under dropout / DropPath is not inspected")
+        if torch.is_grad_enabled():
+            raise VtxError("vtx: attention_inputs runs under torch.no_grad(): none of its outputs has a gradient")
+        flat = self.attention_layers()
+        depth = len(flat)
+        want = set()
+        for l in layers:
+            if not -depth <= int(l) < depth:
+                raise VtxError(f"vtx: attention_inputs: layer {l} of a model of {depth} layers")
+            want.add(int(l) % depth)
+        if not input.is_cuda:
+            raise VtxError("vtx: attention_inputs needs device tensors (there is no CPU fallback), of a SwinTransformer as of a "
+                           "VisionTransformer")
+        taps = {}
+        with VF.weight_scope(self, input), drop_path_scope(self, input.shape[0], input.device):
+            out = self.patch_embedding.forward_nchw(input)
+            index = 0
+            for stage in self.stages():
+                for module in stage:
+                    if hasattr(module, "set_drop_path"):
+                        if index in want:
+                            a = module.attn
+                            a.check_input(out)
+                            normed = module.norm_attn(out)
+                            qkv = VF.LinearFn.apply(normed.to(VF.compute_dtype(normed)), a.weight.weight, a.weight.bias)
+                            mask = None
+                            if a.shift:
+                                mask = a.local_mask.view(torch.uint8) if a.local_mask.dtype == torch.bool else a.local_mask.to(torch.uint8)
+                            taps[index] = AttentionTap(qkv, table_bias(a.rel_pos.weight.detach(), a.pos, a.n_head), mask, a.n_head,
+                                                       a.dim_head, a.input_size, a.window_size, bool(a.shift))
+                        index += 1
+                    out = module(out)
+            norm = self.final_linear[0]
+            out = VF.LayerNormFn.apply(out, norm.weight, norm.bias, norm.eps)
+            out = VF.TokenMeanFn.apply(out)
+            cls = self.classifier[2]
+            return taps, VF.LinearFn.apply(out, cls.weight, cls.bias)
 
     def make_block(self, depth, in_dim, dim, n_head, dim_head, dim_ff, input_size, window_size, reduction, drop_ff,
                    drop_attn):

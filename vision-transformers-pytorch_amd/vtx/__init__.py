@@ -15,14 +15,17 @@
                   cross-entropy kernels), ProbeMeter, linear_probe_evaluate (also reachable as vtx.LinearProbe, ...)
   vtx.attnmap     attention maps and per-head attention statistics without writing P: attention_rows, attention_stats,
                   mass_mask, cls_attention_maps, AttentionStatsMeter, attention_statistics (also reachable as
-                  vtx.attention_rows, ...)
+                  vtx.attention_rows, ...); for window and halo attention (Swin, Twins, Halo): window_attention_rows,
+                  window_attention_stats, halo_attention_rows, halo_attention_stats, WindowAttentionStatsMeter,
+                  window_attention_map
 """
 
 _KNN_NAMES = ("FeatureBank", "KnnMeter", "knn_search", "extract_features", "knn_evaluate", "ShardedFeatureBank",
               "knn_search_sharded")
 _PROBE_NAMES = ("LinearProbe", "ProbeMeter", "linear_probe_evaluate")
 _ATTNMAP_NAMES = ("attention_rows", "attention_stats", "mass_mask", "cls_attention_maps", "AttentionStatsMeter",
-                  "attention_statistics")
+                  "attention_statistics", "window_attention_rows", "window_attention_stats", "halo_attention_rows",
+                  "halo_attention_stats", "WindowAttentionStatsMeter", "window_attention_map")
 
 
 def __getattr__(name):

@@ -1597,6 +1597,36 @@ def attn_map_stats(q, k, n_head, n_prefix=1, grid=None):
     return stats
 
 
+def attn_mapw_rows(q, kv, B, Lq, Lk, n_head, D, swin=None, bias=None, mask=None, row0=0, nrows=1):
+    """Rows row0 .. row0 + nrows - 1 of softmax(q k^T / sqrt(D) + bias, masked cells excluded) of every problem and head of a window /
+    halo attention; operands and checks as attn_hdw_fwd: swin = (H, W, win, shift) with q the packed QKV projection of B images in
+    map order, or swin None with B problems of plain rows (kv None: packed; else the q | kv pair).  Nothing is copied.
+    -> (p fp32 [problems, nH, nrows, Lk], masked cells exactly 0; lse fp32 [problems, nH, nrows]); rules: include/vtx.h."""
+    qv, kk, _, ldq, ldkv, nprob, (H, W, win, shift), mask = _attn_hdw_args(q, kv, B, Lq, Lk, n_head, D, swin, bias, mask)
+    row0, nrows = int(row0), int(nrows)
+    if row0 < 0 or nrows < 1 or row0 + nrows > Lq:
+        raise VtxError(f"vtx: attn_mapw_rows: rows {row0}..{row0 + nrows} of {Lq}")
+    p = torch.empty((nprob, int(n_head), nrows, Lk), dtype=torch.float32, device=q.device)
+    lse = torch.empty((nprob, int(n_head), nrows), dtype=torch.float32, device=q.device)
+    check(_lib.load().vtx_attn_mapw_rows(_p(qv), _p(kk), ldq, ldkv, _p(p), _p(lse), _p(bias), _p(mask), B, Lq, Lk, int(n_head), D, H, W,
+                                         win, shift, row0, nrows, _dt(q), _stream()), "vtx_attn_mapw_rows")
+    return p, lse
+
+
+def attn_mapw_stats(q, kv, B, Lq, Lk, n_head, D, swin=None, bias=None, mask=None, grids=None):
+    """Per-query statistics [lse, entropy, smax, self mass, mean distance] of a window / halo attention without writing P; operands as
+    attn_mapw_rows.  ``grids`` = (gq, gk), halo mode only: the gq x gq queries sit centred in the gk x gk key grid; None: self and
+    distance are 0 (window mode takes its positions from the window).  -> stats fp32 [problems, nH, Lq, 5]; rules: include/vtx.h."""
+    qv, kk, _, ldq, ldkv, nprob, (H, W, win, shift), mask = _attn_hdw_args(q, kv, B, Lq, Lk, n_head, D, swin, bias, mask)
+    gq, gk = (0, 0) if grids is None else (int(grids[0]), int(grids[1]))
+    if grids is not None and swin is not None:
+        raise VtxError("vtx: attn_mapw_stats takes grids in halo mode only (a window gives the positions itself)")
+    stats = torch.empty((nprob, int(n_head), Lq, 5), dtype=torch.float32, device=q.device)
+    check(_lib.load().vtx_attn_mapw_stats(_p(qv), _p(kk), ldq, ldkv, _p(stats), _p(bias), _p(mask), B, Lq, Lk, int(n_head), D, H, W, win,
+                                          shift, gq, gk, _dt(q), _stream()), "vtx_attn_mapw_stats")
+    return stats
+
+
 def attn_map_meter(stats, meter, layer, n_prefix=1):
     """Add ``stats`` fp32 [B, nH, Lq, 5] to ``meter`` float64 [n_layer, nH, 6] at ``layer`` (include/vtx.h has the six values)."""
     _dev(stats, meter)
@@ -1703,7 +1733,7 @@ def vit_assemble_bwd(dx):
 
 
 # ------------------------------------------------------------------------------- attention: vtx/attention.py, reached through this module
-from .attention import (SHORT_MAX, _drop_args, _pos_inverse, _sattn_cfg, attention_bwd, attention_fwd, attn_hd_bwd,        # noqa: E402,F401
+from .attention import (SHORT_MAX, _attn_hdw_args, _drop_args, _pos_inverse, _sattn_cfg, attention_bwd, attention_fwd, attn_hd_bwd,        # noqa: E402,F401
                         attn_hd_fwd, attn_hd_pad, attn_hd_routes, attn_hd_supported, attn_hdw_bwd, attn_hdw_fwd, attn_hdw_routes,
                         attn_keep_mask, generic_label, pos_csr, relpos_bias, srattn_bwd, srattn_fwd, srattn_scores, table_bias,
                         table_bias_bwd, wattn_bwd, wattn_bwd_kernel_name, wattn_fwd, wattn_fwd_kernel_name, wattn_supported,
