@@ -6,7 +6,9 @@ never a measured number: each builder below computes it in fp64 from the arithme
 absolute-value products, and carries its derivation.  tests/test_elementwise_host.py proves every builder on the CPU (a torch
 model of a correct kernel has zero violations; planted defects are found and located); tests/test_gpu_elementwise.py and
 tests/test_gpu_attn_drop_elementwise.py (attention dropout, the generic window path) run the kernels against them;
-tests/test_gpu_layer_elementwise.py runs their row-mapped instances, launch by launch through a compacted one-call layer.
+tests/test_gpu_layer_elementwise.py runs their row-mapped instances, launch by launch through a compacted one-call layer;
+tests/test_gpu_sr_layer_elementwise.py does the same for the one-call PVT block / Twins global half, and tests/test_gpu_sr_kernels.py
+holds the depthwise 3x3 convolution of Twins' positional encoding to dwconv_env / dwconv_wgrad_env.
 
 Conventions, stated once:
   U32 = 2^-24   unit roundoff of an fp32 operation (every accumulator, every epilogue expression)
@@ -106,10 +108,14 @@ def check_elementwise(name, got, ref, env, layout=None, family=None):
     return wr
 
 
-def log_worst():
-    """One parity.log line per family with the worst ratio of this process (called by the GPU file's last test)."""
-    for fam in sorted(WORST):
-        _log(f"elementwise family {fam:28s} worst |err|/env {WORST[fam]:.3f}")
+def log_worst(prefix=""):
+    """One parity.log line per family (whose name starts with ``prefix``) with the worst ratio of this process (called by a GPU file's last
+    test).  -> {family: ratio} of the lines written."""
+    mine = {fam: r for fam, r in WORST.items() if fam.startswith(prefix)}
+    for fam in sorted(mine):
+        ratio = f"{mine[fam]:.3f}" if mine[fam] >= 0.0005 else f"{mine[fam]:.1e}"        # (an fp32-sum family can sit far below three decimals)
+        _log(f"elementwise family {fam:28s} worst |err|/env {ratio}")
+    return mine
 
 
 # ======================================================================================================= activations
@@ -136,6 +142,12 @@ def dsilu_env(z):
     return v, (1 + z.abs()) * s * es + 4 * U32 * (s + z.abs() * s * (1 - s))
 
 
+def d2silu_abs(z):
+    """|silu''(z)| = |s (1 - s) (2 + z (1 - 2 s))| (at most 1 / 2, at z = 0): the slope of silu' that carries an error of z into silu'(z)."""
+    s = torch.sigmoid(z)
+    return (s * (1 - s) * (2 + z * (1 - 2 * s))).abs()
+
+
 def _erf_abs_err(z):
     # erf_as = 1 - poly(t) e, e = __expf(-z^2 / 2): the documented 1.5e-7, plus the fp32 evaluation of poly (rcp, 5 Horner steps, product:
     # 8 U32 relative) and of e (E_EXP + (z^2 / 2) 2 U32 relative) on the term poly e = 1 - erf <= 1
@@ -159,7 +171,7 @@ DACT = {"silu": dsilu_env, "gelu": dgelu_env}
 
 
 # ======================================================================================================= GEMM
-def gemm_env(a, w_nk, out_dtype, bias=None, rowscale=None, rows_per_scale=1, resid=None, dact=None, z_in=None, a_err=None):
+def gemm_env(a, w_nk, out_dtype, bias=None, rowscale=None, rows_per_scale=1, resid=None, dact=None, z_in=None, a_err=None, z_err=None):
     """vtx_gemm without a forward activation: C = resid + rowscale[row / rps] * ((a . w^T + bias) [* act'(z_in)]); a [M, K], w_nk [N, K]
     (pass w.t() of a mode-1 weight).  -> (ref, env).
 
@@ -171,7 +183,12 @@ def gemm_env(a, w_nk, out_dtype, bias=None, rowscale=None, rows_per_scale=1, res
     to the output type: u_out |ref|.
         env = TWO * ( u_out |ref| + (K + n_epi) U32 S [+ rowscale |acc| e'] )
     ``a_err`` (a fused launch whose row operand is never stored): a per-element bound on the kernel's a, carried through the same linear
-    map: + rowscale * (a_err . |w|) [* |act'|]."""
+    map: + rowscale * (a_err . |w|) [* |act'|].
+    ``z_err`` (dact = 'silu' on a pre-activation the kernel RECOMPUTES and never stores, the fused MLP backward): a per-element bound on the
+    kernel's z against ``z_in``; act' moves by at most |act''(z_in)| z_err to first order: + rowscale |acc| |silu''(z_in)| z_err.  The
+    remainder, |silu'''| z_err^2 |acc| / 2 with |silu'''| <= 0.31, matters only near the zeros of silu'' (|z| about 2.4); with z_err at one
+    bf16 spacing of z it is at most 0.03 of u_out |acc act'| plus the first-order term (largest at z = -2.4, where act' is -0.1): a
+    second-order term, inside the factor TWO like every other."""
     A, W = f64(a), f64(w_nk)
     K = A.shape[1]
     acc = A @ W.t()
@@ -185,6 +202,9 @@ def gemm_env(a, w_nk, out_dtype, bias=None, rowscale=None, rows_per_scale=1, res
     if dact is not None:
         d, ed = DACT[dact](f64(z_in))
         extra = acc.abs() * ed
+        if z_err is not None:
+            assert dact == "silu"
+            extra = extra + acc.abs() * d2silu_abs(f64(z_in)) * f64(z_err)
         acc, S, lin, n_epi = acc * d, S * d.abs(), lin * d.abs(), n_epi + 1
     if rowscale is not None:
         rs = f64(rowscale).repeat_interleave(rows_per_scale)[:A.shape[0], None]
@@ -227,6 +247,59 @@ def wgrad_env(dy, x, rowscale=None, rows_per_scale=1, scale_const=0.0, slices=1)
     rW, SW = c * (D.t() @ X), c * (D.abs().t() @ X.abs())
     rb, Sb = c * D.sum(0), c * D.abs().sum(0)
     return (rW, TWO * (U32 * rW.abs() + n * U32 * SW)), (rb, TWO * (U32 * rb.abs() + n * U32 * Sb))
+
+
+# ======================================================================================================= depthwise 3x3 convolution
+def _dw_taps(X, Wt, adjoint):
+    """X [B, H, W, C] fp64, Wt [C, 9] fp64 -> the nine zero-padded tap products [9, B, H, W, C] of the correlation
+    (tap k = ky * 3 + kx reads pixel (y + ky - 1, x + kx - 1) of the SAME image; adjoint: weight 8 - k at offset k) and the 0 / 1
+    liveness of each tap [9, 1, H, W, 1] (dead = the pixel read lies outside the image)."""
+    B, H, W, C = X.shape
+    pad = torch.zeros((B, H + 2, W + 2, C), dtype=torch.float64)
+    pad[:, 1:H + 1, 1:W + 1] = X
+    one = torch.zeros((1, H + 2, W + 2, 1), dtype=torch.float64)
+    one[:, 1:H + 1, 1:W + 1] = 1.0
+    taps, live = [], []
+    for k in range(9):
+        ky, kx = divmod(k, 3)
+        taps.append(pad[:, ky:ky + H, kx:kx + W] * Wt[:, 8 - k if adjoint else k])
+        live.append(one[:, ky:ky + H, kx:kx + W])
+    return torch.stack(taps), torch.stack(live)
+
+
+def dwconv_env(x, w, out_dtype, adjoint=False):
+    """vtx_dwconv3_fwd: y = x + sum_k w[c][k] x[pixel + offset(k)][c] on channels-last [B, H, W, C], w [C, 1, 3, 3] fp32, zero padding per
+    image; adjoint: the mirrored taps (w[c][8 - k] at offset k).  -> (ref, env) [B, H, W, C].
+
+    Derivation.  A pixel with n_live live taps (4 in a corner, 6 on an edge, 9 inside; fewer where H or W is below 3) is the residual plus
+    n_live products accumulated in fp32, in any order, each product rounded on its own or fused into its add: at most one U32 per product and
+    one per addition, every one on a quantity bounded by S = |x| + sum_live |w||x|:  (2 n_live) U32 S.  A dead tap adds nothing: it is no
+    term of S.  The store rounds once to the output type: u_out |ref|.
+        env = TWO * ( u_out |ref| + 2 n_live U32 S )"""
+    X, Wt = f64(x), f64(w).reshape(-1, 9)
+    taps, live = _dw_taps(X, Wt, adjoint)
+    ref = X + taps.sum(0)
+    S = X.abs() + taps.abs().sum(0)
+    n_live = live.sum(0)                                        # [1, H, W, 1]
+    return ref, TWO * (u_of(out_dtype) * ref.abs() + 2 * n_live * U32 * S)
+
+
+def dwconv_wgrad_env(x, dy):
+    """vtx_dwconv3_wgrad: dw[c][k] = sum over the pixels whose tap k is live of dy[pixel][c] x[pixel + offset(k)][c], fp32, written.
+    -> (ref, env) [C, 9].
+
+    Derivation.  n = B * (live pixels of tap k) products summed in fp32 in any order (pixel lanes, rows of a workgroup, the workgroups'
+    partial sums, the reduce kernel's slices): (n - 1) U32 sum|t|; each product may round once more (fp32 operands): U32 sum|t|; the value is
+    stored in fp32 as computed.  A product with a zero factor is an exact zero whatever the order, so an output whose terms all vanish has
+    env = 0: it must be an exact zero.
+        env = TWO * n U32 sum|t|"""
+    X, D = f64(x), f64(dy)
+    B = X.shape[0]
+    taps, live = _dw_taps(X, torch.ones((X.shape[-1], 9), dtype=torch.float64), False)     # x[pixel + offset(k)]
+    t = taps * D                                                                           # [9, B, H, W, C]
+    n = B * live.sum((1, 2, 3, 4))                                                         # [9]
+    ref, S = t.sum((1, 2, 3)).t(), t.abs().sum((1, 2, 3)).t()                              # [C, 9]
+    return ref, TWO * n[None] * U32 * S
 
 
 # ======================================================================================================= LayerNorm

@@ -101,6 +101,94 @@ def bias_cast(x, bias, dtype):
     return y.to(dtype)
 
 
+# ------------------------------------------------------------------------------------------ bit-level restatements (fp32 in, fp32 order)
+# The kernels below are ONE fp32 add per element, or a sum in a documented fixed order: the restatement does the same IEEE fp32
+# operations in the same order (torch's CPU float32 arithmetic), so the GPU tests demand the bits (tests/test_gpu_sr_kernels.py).
+def add_pos_fwd(x, cls, pos):
+    """csrc/pvt_misc.hip add_pos_fwd_kernel: out[b, 0] = T(cls + pos[0]) (cls given), out[b, s + t] = T(float(x[b, t]) + pos[s + t])."""
+    B, T, C = x.shape
+    s = 0 if cls is None else 1
+    out = torch.empty((B, T + s, C), dtype=x.dtype)
+    out[:, s:] = (x.float() + pos[s:].float()[None]).to(x.dtype)
+    if s:
+        out[:, 0] = (cls.float() + pos[0].float()).to(x.dtype)[None]
+    return out
+
+
+def add_pos_bwd(dout, s, lanes=16):
+    """csrc/pvt_misc.hip add_pos_bwd_kernel: dx = dout[:, s:] (a copy); dpos[t] = the fp32 sum over the batch in the kernel's order --
+    batch lane l adds b = l, l + 16, ... in sequence starting from 0.f, then the lanes 0 .. 15 are added in lane order starting from 0.f;
+    dcls = dpos[0] (s = 1).  ``lanes`` = 1 restates the plain batch order (what a defect test plants).  -> (dx, dcls or None, dpos)."""
+    d = dout.float()
+    B = d.shape[0]
+    acc = torch.zeros((lanes,) + tuple(d.shape[1:]), dtype=torch.float32)
+    for b in range(B):
+        acc[b % lanes] = acc[b % lanes] + d[b]
+    dpos = torch.zeros(tuple(d.shape[1:]), dtype=torch.float32)
+    for l in range(lanes):
+        dpos = dpos + acc[l]
+    return dout[:, s:].clone(), (dpos[0].clone() if s else None), dpos
+
+
+def patch_index(B, H, W, C, p, skip):
+    """Flat element index into x [B, skip + H W, C] of every element of the patch matrix [B (H/p) (W/p), p p C], columns (py, px, c)
+    (csrc/pvt_misc.hip patchify_kernel)."""
+    tok = torch.arange(B * (skip + H * W) * C).reshape(B, skip + H * W, C)[:, skip:].reshape(B, H // p, p, W // p, p, C)
+    return tok.permute(0, 1, 3, 2, 4, 5).reshape(-1)
+
+
+def twins_index(B, H, W, C, r):
+    """Flat element index into x [B, H, W, C] of every element of the patch matrix [B (H/r) (W/r), C r r], columns (c', py, px), of
+    Twins-SVT's reduction conv with the reference's reshape kept as written (csrc/twins_misc.hip twins_subsample_kernel's index map)."""
+    n = H * W * C
+    e = torch.arange(n)
+    K, rr, Wr = r * r * C, r * r, W // r
+    t, col = e // K, e % K
+    cp, pp = col // rr, col % rr
+    py, px = pp // r, pp % r
+    i, j = t // Wr, t % Wr
+    f = cp * H * W + (i * r + py) * W + (j * r + px)
+    w, rem = f // (H * C), f % (H * C)
+    h, c = rem // C, rem % C
+    xi = (h * W + w) * C + c
+    return (torch.arange(B)[:, None] * n + xi[None]).reshape(-1)
+
+
+def scatter_accumulate(dx, g, index):
+    """dx.flat[index[i]] = T(float(dx.flat[index[i]]) + float(g.flat[i])): one fp32 add and one rounding per element of a permutation
+    scatter (vtx_patchify_bwd / vtx_twins_subsample_bwd with accumulate = 1); elements no index names keep their bits."""
+    out = dx.clone().reshape(-1)
+    out[index] = (out[index].float() + g.reshape(-1).float()).to(dx.dtype)
+    return out.reshape(dx.shape)
+
+
+def halo_windows(H, W, win, halo):
+    """[(wi, wj, y0, y1, x0, x1, ky0, kx0)] in ascending (wi, wj): the part [y0, y1) x [x0, x1) of the map that window (wi, wj)'s
+    neighbourhood covers and the neighbourhood cell (ky0, kx0) of its first pixel."""
+    side = win + 2 * halo
+    res = []
+    for wi in range(H // win):
+        for wj in range(W // win):
+            ya, xa = wi * win - halo, wj * win - halo
+            y0, y1, x0, x1 = max(ya, 0), min(ya + side, H), max(xa, 0), min(xa + side, W)
+            res.append((wi, wj, y0, y1, x0, x1, y0 - ya, x0 - xa))
+    return res
+
+
+def halo_scatter(src, mp, B, H, W, c0, nc, win, halo):
+    """csrc/halo.hip halo_scatter_kernel: channels [c0, c0 + nc) of the map [B, H, W, ld] = T(the fp32 sum, from 0.f, over the windows
+    whose neighbourhood holds the token, in ascending (wi, wj) order, of src [B nW, side^2, nc]); the other channels keep their bits."""
+    side, nWx = win + 2 * halo, W // win
+    nW = (H // win) * nWx
+    s = src.float().reshape(B, nW, side, side, nc)
+    acc = torch.zeros((B, H, W, nc), dtype=torch.float32)
+    for wi, wj, y0, y1, x0, x1, ky0, kx0 in halo_windows(H, W, win, halo):
+        acc[:, y0:y1, x0:x1] = acc[:, y0:y1, x0:x1] + s[:, wi * nWx + wj, ky0:ky0 + (y1 - y0), kx0:kx0 + (x1 - x0)]
+    out = mp.clone()
+    out[..., c0:c0 + nc] = acc.to(mp.dtype)
+    return out
+
+
 def table_bias(table, pos, n_head):
     """bias[h][cell...] = table[pos[cell...]][h]."""
     t = table[pos.reshape(-1)].reshape(tuple(pos.shape) + (n_head,))

@@ -287,7 +287,12 @@ static bool sub_geom(SubGeom& g, int H, int W, int C, int r) {
   g.mC = sub_magic(C);
   const uint64_t n = (uint64_t)H * W * C;
   const uint64_t dmax = (uint64_t)(g.K > g.HC ? g.K : g.HC);
-  return n * dmax < (1ull << 32);
+  // a divisor of 1 has no 32-bit reciprocal (ceil(2^32 / 1) wraps to 0): its quotient comes out 0, which is right only while the dividend
+  // is 0 too.  Wr == 1: t / Wr with t < H / r (the 7 x 7, r = 7 map of Twins-SVT-S stage 4 has t = 0 only and keeps the reciprocal form);
+  // r == 1: col / rr with col < C; C == 1: rem / C with rem < H and, at H == 1, f / HC with f < W.  Where a dividend can be non-zero the
+  // permutation came out scrambled: those geometries take the plain-division instantiation
+  const bool unit = (g.Wr == 1 && H > r) || (r == 1 && C > 1) || (C == 1 && (H > 1 || W > 1));
+  return !unit && n * dmax < (1ull << 32);
 }
 template <typename T, bool BWD, bool ACC>
 static void sub_launch(const void* src, void* dst, void* dst_t, int B, int H, int W, int C, int r, hipStream_t st) {
