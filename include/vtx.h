@@ -1092,6 +1092,41 @@ int vtx_attn_mapw_stats(const void* q, const void* k, int64_t ldq, int64_t ldkv,
                         const uint8_t* mask, int B, int Lq, int Lk, int nH, int D, int H, int W, int win, int shift, int gq, int gk,
                         int dtype, void* stream);
 
+/* ---- Weighted column sums of P (csrc/attention_maps.hip): the primitive of attention rollout -- a row vector pushed through
+ * A_l = residual I + (1 - residual) mean_h P_l, layer by layer -- and of the mean attention a key token receives.  The entries
+ * above keep their bits and their code.
+ *
+ * Operands: q, k, ldq, ldkv, B, Lq, Lk, nH, D, dtype exactly as vtx_attn_map_rows takes them (bf16 or fp32, D a multiple of 8 in
+ *   8..128, the packed projection or the q | kv pair by pointer and stride).  w fp32 [B, R, Lq], 1 <= R <= 16, shared by the
+ *   heads; any finite values, negative ones included.
+ * Probabilities: s, m, l and p_ij = __expf(s_ij - m_i) / l_i are formed as vtx_attn_map_rows forms them -- the same passes, the
+ *   same lane order, the same butterfly, the IEEE division: p_ij is bit for bit the value that entry stores.
+ * Column sums: t = w[b, r, i] * p_ij is one fp32 product, rounded on its own (never one fma with the add); c[b, h, r, j] is the
+ *   fp32 sum of t over i in an order that depends on Lq alone, not on B, R, the launch geometry or the other weight rows of the
+ *   call: queries in tiles of 16; wave v of 4 adds, per query lane i % 16, its tiles v, v + 4, v + 8, .. in ascending order from
+ *   0.f; the 16 query lanes meet in one fixed butterfly; the four waves are added in wave order.  c is stored to out_heads fp32
+ *   [B, nH, R, Lk], or kept in the workspace when out_heads is NULL.
+ * Blend: out_mix fp32 [B, R, Lk] (optional; needs Lq == Lk) = (alpha * w[b, r, j]) + (beta * (c_0 + c_1 + .. + c_{nH-1})), the
+ *   heads summed in ascending order, every product and sum one fp32 operation in that written order, none contracted into an
+ *   fma.  At least one of out_heads and out_mix is non-NULL.
+ * Bits: an image's outputs are the same bits however the batch is cut into calls; a weight row's whatever other rows share the
+ *   call; the same for the packed projection and a split copy, and for either output asked for alone or both.  A zero weight
+ *   contributes an exact zero, so a one-hot weight row w = e_i makes out_heads[b, h, r, :]
+ *   bit-equal to the row vtx_attn_map_rows stores for query i (and 2^-3 e_i to that row times 2^-3); alpha = 1, beta = 0
+ *   returns w.
+ * P is never written: no buffer of Lq * Lk exists per problem.  The workspace holds (m, l) per query and room for c:
+ *   vtx_attn_map_colsum_workspace_bytes = 4 * (2 B nH Lq + B nH R Lk) bytes (0 for sizes the entry refuses).  Three launches on
+ *   `stream`: (m, l); the column sums; the blend (only with out_mix).  No floating-point atomics.
+ *
+ * Errors, all before any launch, with the codes of the vtx_attn_map entries: VTX_ERR_NULL (q, k, w, or both outputs NULL),
+ * VTX_ERR_DTYPE, VTX_ERR_SHAPE (B, Lq, Lk or nH < 1; D outside the multiples of 8 in 8..128; R outside 1..16; out_mix with
+ * Lq != Lk; a stride below nH * D; B * Lq or B * Lk >= 2^31 - 1; alpha or beta not finite), VTX_ERR_ALIGN (a stride that is not a
+ * multiple of 8; q or k off 16 bytes; an fp32 pointer or the workspace off 4), VTX_ERR_WORKSPACE (ws NULL or ws_bytes short). */
+size_t vtx_attn_map_colsum_workspace_bytes(int B, int Lq, int Lk, int nH, int R);
+int vtx_attn_map_colsum(const void* q, const void* k, int64_t ldq, int64_t ldkv, const float* w, float* out_heads, float* out_mix,
+                        float alpha, float beta, int B, int Lq, int Lk, int nH, int D, int R, void* ws, size_t ws_bytes, int dtype,
+                        void* stream);
+
 /* ---- Multi-tensor weight cast (csrc/cast.hip): all fp32 Linear / Conv weights of a model -> bf16, plain [out][in]
  * and transposed [in][out], in one launch per forward.  This is the per-call weight cast of the reference's bf16
  * autocast (torch.cuda.amp.autocast around model(input), train.py:273-274) done once for the whole model.

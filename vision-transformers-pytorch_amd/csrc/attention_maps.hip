@@ -72,9 +72,42 @@
 //   With win == 0 and no bias, mask or grids, p, lse and slots 0..2 are the bits of vtx_attn_map_rows / _stats on the same operands.
 //   Slot 3 sits where the prefix mass sits: vtx_attn_map_meter with n_prefix = 0 sums [queries, entropy, self, dist, queries, max smax].
 //
+// WEIGHTED COLUMN SUMS OF P (vtx_attn_map_colsum; new kernels only, the instantiations above are what they were): the primitive of
+// attention rollout (a row vector pushed through A_l = residual I + (1 - residual) mean_h P_l) and of the attention a key RECEIVES.
+// Operands q, k, ldq, ldkv, B, Lq, Lk, nH, D, dtype exactly as vtx_attn_map_rows; w fp32 [B, R, Lq], 1 <= R <= 16, shared by the heads,
+// any finite values, negative ones included.  Term by term:
+//   probabilities  s, m, l and p_ij = __expf(s_ij - m_i) / l_i as vtx_attn_map_rows forms them.  Launch 1 (attn_map_ml_kernel) IS passes 1
+//                  and 2 of attn_map_rows_kernel -- the same AmRow, the same lanes and order, the same butterfly -- and stores (m_i, l_i)
+//                  to the workspace, fp32 [B, nH, Lq, 2].  Launch 2 forms s_ij by am_scores and p_ij by the same expression with the
+//                  IEEE division: p_ij is bit for bit the value vtx_attn_map_rows stores.
+//   column sums    t = w[b, r, i] * p_ij is ONE fp32 product, rounded on its own, and c[b, h, r, j] the fp32 sum of the t over i: the
+//                  product and the add are NEVER contracted into an fma (am_wacc settles the rounded product in a register), so the arithmetic
+//                  is the same in every instantiation.  THE ORDER depends on Lq alone.  A workgroup of 4 waves owns one key block of
+//                  64 keys of one (image, head) and ALL queries, in tiles of 16 (tile t = queries 16 t .. 16 t + 15, query i in lane
+//                  column i % 16):
+//                    wave v, per lane and key, from 0.f:   a_v[i % 16] += t_i   over its tiles t = v, v + 4, v + 8, .. ascending
+//                    the 16 query lanes meet in one butterfly (group_sum<16>, DPP):   x += x(lane ^ 1);  x += x(lane ^ 2);
+//                      x += x(lane ^ 7);  x += x(lane ^ 15)   -- after the first two steps the lanes of a quad hold one value, so
+//                      these are the sums of the xor-4 and xor-8 steps; every lane ends with the same bits
+//                    the waves meet in LDS in wave order:   c = ((x_0 + x_1) + x_2) + x_3     (a wave without a tile holds 0.f)
+//                  Neither B, R, the launch geometry nor the other weight rows of the call enter: a call of more than 4 weight rows
+//                  recomputes the scores per chunk of 4 rows, each row's own accumulators apart.  A zero weight contributes an exact
+//                  zero (p is finite), so a one-hot row w = e_i gives c[b, h, r, :] = 0.f + .. + 1.f * p_i: + .. + 0.f = the row
+//                  p[b, h, i, :] that vtx_attn_map_rows stores, bit for bit (and 2^-3 e_i that row times 2^-3).
+//                  c goes to out_heads fp32 [B, nH, R, Lk], or to the workspace when that pointer is null.
+//   blend          out_mix fp32 [B, R, Lk] (Lq == Lk), launch 3, one thread per element:
+//                    h_sum = (..((c_0 + c_1) + c_2) + ..) + c_{nH - 1}     heads ascending
+//                    out_mix[b, r, j] = (alpha * w[b, r, j]) + (beta * h_sum)
+//                  two fp32 products and one fp32 sum in that written order, NOT contracted (am_blend settles both products): the envelope
+//                  charges one rounding each.  alpha = 1, beta = 0 returns w.
+//   bits           an image's outputs do not depend on how the batch is cut into calls, a weight row's not on the other rows of the
+//                  call, neither on packed against split operands nor on which of the two outputs are asked for.
+// P is never written by vtx_attn_map_colsum and no buffer of Lq * Lk exists per problem: the workspace is (m, l) per query and, without
+// out_heads, c: 4 * (2 B nH Lq + B nH R Lk) bytes (vtx_attn_map_colsum_workspace_bytes).
+//
 // No floating-point atomics anywhere; every sum has a fixed order, so the same inputs give the same bits.
 //
-// Budget (hipcc resource remarks, gfx950, no scratch in any instantiation): DESIGN.md sections 7i and 7j.
+// Budget (hipcc resource remarks, gfx950, no scratch in any instantiation): DESIGN.md sections 7i, 7j and 7k.
 #include "vtx_common.h"
 
 #define AM_KB 64                 // keys per block (4 tiles of 16)
@@ -501,7 +534,149 @@ __global__ __launch_bounds__(256) void attn_mass_mask_kernel(const float* __rest
     if (e0 + i < n) dst[(unsigned)(srt[e0 + i] & 0xffffffffull)] = w[i] > thr ? 1 : 0;
 }
 
+// ------------------------------------------------------------------------------------------------- weighted column sums of P
+#define AM_RMAX 16               // weight rows of a call at most
+#define AM_RC 4                  // weight rows per chunk: 16 accumulators each, the scores recomputed per chunk
+
+// One product and one sum, each rounded on its own: never an fma, whatever the instantiation around it (WEIGHTED COLUMN SUMS).  The build
+// contracts wherever it can (-ffp-contract=fast), so the rounded product is settled in a register before the add, as acc_settle does.
+__device__ __forceinline__ float am_settle(float t) { asm volatile("" : "+v"(t)); return t; }
+__device__ __forceinline__ float am_wacc(float acc, float w, float p) { return acc + am_settle(w * p); }
+// out_mix = (alpha * w) + (beta * h_sum): two rounded products and a sum in that order, not contracted.
+__device__ __forceinline__ float am_blend(float alpha, float w, float beta, float hsum) {
+  return am_settle(alpha * w) + am_settle(beta * hsum);
+}
+
+// launch 1: passes 1 and 2 of attn_map_rows_kernel for all Lq rows (g.row0 = 0, g.nrows = Lq); ml [B, nH, Lq, 2] = (m, l).
+// grid = B * nH * ceil(Lq / 64)
+template <typename T, int DP>
+__global__ __launch_bounds__(256) void attn_map_ml_kernel(const T* __restrict__ qp, const T* __restrict__ kp, float* __restrict__ ml,
+                                                         AmGeom g) {
+  constexpr int DS = DP / 32;
+  AmRow<T, DS> row;
+  row.init(qp, kp, g);
+  if (row.wave_idle(g)) return;
+  row.pass_max(g);
+  const float m = row.m;
+  float l = 0.f;
+  for (int k0 = 0; k0 < g.Lk; k0 += AM_KB) {
+    f32x4 st[4];
+    const unsigned live = row.scores(st, k0, g);
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (row.counts(live, kt, r, k0 + kt * 16 + row.g_ * 4 + r, g)) l += __expf(st[kt][r] - m);
+  }
+  l = am_join(l);
+  if (row.qv && row.g_ == 0) {
+    float* o = ml + ((int64_t)row.bh * g.Lq + row.qi) * 2;
+    o[0] = m;
+    o[1] = l;
+  }
+}
+
+// launch 2: grid = B * nH * kblocks (kblocks = ceil(Lk / 64)); a workgroup owns key block k0 .. k0 + 63 of (image b, head h) and every
+// query; c [B, nH, R, Lk].  RC = weight rows per chunk (1: the single row of a CLS rollout; AM_RC otherwise).
+template <typename T, int DP, int RC>
+__global__ __launch_bounds__(256) void attn_map_colsum_kernel(const T* __restrict__ qp, const T* __restrict__ kp,
+                                                             const float* __restrict__ ml, const float* __restrict__ w,
+                                                             float* __restrict__ c, AmGeom g, int R, int kblocks) {
+  constexpr int DS = DP / 32;
+  __shared__ float red[4][RC][AM_KB];
+  const int bh = blockIdx.x / kblocks;
+  const int k0 = (blockIdx.x - bh * kblocks) * AM_KB;
+  const int b = bh / g.nH, h = bh - b * g.nH;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c_ = lane & 15, g_ = lane >> 4;
+  const T* qb = qp + h * g.D;
+  const T* kb = kp + h * g.D;
+  const int64_t qrow0 = (int64_t)b * g.Lq, krow0 = (int64_t)b * g.Lk;
+  const float* mlb = ml + (int64_t)bh * g.Lq * 2;
+  const int ntiles = (g.Lq + 15) / 16;
+  for (int r0 = 0; r0 < R; r0 += RC) {
+    f32x4 acc[RC][4];
+#pragma unroll
+    for (int rr = 0; rr < RC; ++rr)
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) acc[rr][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int t = wave; t < ntiles; t += 4) {                          // wave-uniform: the MFMAs run with every lane
+      const int q = t * 16 + c_;
+      const bool qv = q < g.Lq;
+      const T* qrow = qb + (qrow0 + (qv ? q : 0)) * g.ldq;
+      Vec8<T> qf[DS];
+#pragma unroll
+      for (int ds = 0; ds < DS; ++ds) qf[ds] = am_load<T>(qrow, ds * 32 + g_ * 8, g.D, qv);
+      float m = 0.f, l = 1.f, wq[RC];
+      if (qv) { m = mlb[2 * q]; l = mlb[2 * q + 1]; }
+#pragma unroll
+      for (int rr = 0; rr < RC; ++rr) wq[rr] = (qv && r0 + rr < R) ? w[((int64_t)b * R + r0 + rr) * g.Lq + q] : 0.f;
+      f32x4 st[4];
+      am_scores<T, DS>(st, qf, kb, krow0, g.ldkv, k0, g.Lk, g.D, g.scale, c_, g_);
+      if (qv) {
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (k0 + kt * 16 + g_ * 4 + r < g.Lk) {
+              const float p = __expf(st[kt][r] - m) / l;               // the expression of attn_map_rows_kernel
+#pragma unroll
+              for (int rr = 0; rr < RC; ++rr) acc[rr][kt][r] = am_wacc(acc[rr][kt][r], wq[rr], p);
+            }
+      }
+    }
+#pragma unroll
+    for (int rr = 0; rr < RC; ++rr)
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float x = group_sum<16>(acc[rr][kt][r]);                     // the butterfly of a key's 16 query lanes (DPP)
+          vmem_guard(x);                                               // LDS store data: one wait state behind packed math
+          if (c_ == 0) red[wave][rr][kt * 16 + g_ * 4 + r] = x;
+        }
+    __syncthreads();
+    for (int i = threadIdx.x; i < RC * AM_KB; i += 256) {
+      const int rr = i / AM_KB, j = i - rr * AM_KB;
+      if (r0 + rr < R && k0 + j < g.Lk) {
+        float s = red[0][rr][j];                                       // the waves in wave order
+        s += red[1][rr][j];
+        s += red[2][rr][j];
+        s += red[3][rr][j];
+        c[((int64_t)bh * R + r0 + rr) * g.Lk + k0 + j] = s;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// launch 3: out [B, R, L] = (alpha * w) + (beta * sum_h c[b, h, r, j]), heads ascending; one thread per element
+__global__ __launch_bounds__(256) void attn_map_mix_kernel(const float* __restrict__ c, const float* __restrict__ w, float* __restrict__ out,
+                                                          float alpha, float beta, int64_t n, int nH, int R, int L) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t rl = (int64_t)R * L;
+  const int64_t b = i / rl, rj = i - b * rl;
+  const float* cp = c + b * nH * rl + rj;
+  float s = cp[0];
+  for (int h = 1; h < nH; ++h) s += cp[h * rl];
+  out[i] = am_blend(alpha, w[i], beta, s);
+}
+
 // ------------------------------------------------------------------------------------------------- host
+template <typename T, int DP> static int am_ml_t(const void* q, const void* k, float* ml, int B, const AmGeom& g, hipStream_t st) {
+  hipLaunchKernelGGL((attn_map_ml_kernel<T, DP>), dim3((unsigned)(B * g.nH * g.qblocks)), dim3(256), 0, st, (const T*)q, (const T*)k, ml, g);
+  return vtx_check_launch();
+}
+template <typename T, int DP> static int am_colsum_t(const void* q, const void* k, const float* ml, const float* w, float* c, int B, int R,
+                                                     int kblocks, const AmGeom& g, hipStream_t st) {
+  const dim3 grid((unsigned)(B * g.nH * kblocks));
+  if (R == 1)
+    hipLaunchKernelGGL((attn_map_colsum_kernel<T, DP, 1>), grid, dim3(256), 0, st, (const T*)q, (const T*)k, ml, w, c, g, R, kblocks);
+  else
+    hipLaunchKernelGGL((attn_map_colsum_kernel<T, DP, AM_RC>), grid, dim3(256), 0, st, (const T*)q, (const T*)k, ml, w, c, g, R, kblocks);
+  return vtx_check_launch();
+}
 template <typename T, int DP> static int am_rows_t(const void* q, const void* k, float* p, float* lse, int B, const AmGeom& g, hipStream_t st) {
   hipLaunchKernelGGL((attn_map_rows_kernel<T, DP>), dim3((unsigned)(B * g.nH * g.qblocks)), dim3(256), 0, st, (const T*)q, (const T*)k, p,
                      lse, g);
@@ -629,6 +804,41 @@ int vtx_attn_mapw_stats(const void* q, const void* k, int64_t ldq, int64_t ldkv,
   if (!am_aligned(q, 15) || !am_aligned(k, 15) || !am_aligned(stats, 3) || !am_aligned(bias, 3)) return VTX_ERR_ALIGN;
   hipStream_t st = (hipStream_t)stream;
   return AM_DISPATCH(amw_stats_t, q, k, stats, (int)nprob, g, st);
+}
+
+/* include/vtx.h: vtx_attn_map_colsum_workspace_bytes -- (m, l) per query and room for c [B, nH, R, Lk]; 0 for sizes the entry refuses */
+size_t vtx_attn_map_colsum_workspace_bytes(int B, int Lq, int Lk, int nH, int R) {
+  if (B <= 0 || Lq <= 0 || Lk <= 0 || nH <= 0 || R < 1 || R > AM_RMAX) return 0;
+  return ((size_t)2 * B * nH * Lq + (size_t)B * nH * R * Lk) * sizeof(float);
+}
+
+/* include/vtx.h: vtx_attn_map_colsum */
+int vtx_attn_map_colsum(const void* q, const void* k, int64_t ldq, int64_t ldkv, const float* w, float* out_heads, float* out_mix,
+                        float alpha, float beta, int B, int Lq, int Lk, int nH, int D, int R, void* ws, size_t ws_bytes, int dtype,
+                        void* stream) {
+  if (!q || !k || !w || (!out_heads && !out_mix)) return VTX_ERR_NULL;
+  AmGeom g;
+  int rc = am_geom(g, B, Lq, Lk, nH, D, 0, Lq > 0 ? Lq : 1, dtype, ldq, ldkv);
+  if (rc) return rc;
+  if (R < 1 || R > AM_RMAX) return VTX_ERR_SHAPE;
+  if (out_mix && Lq != Lk) return VTX_ERR_SHAPE;
+  if (!(fabsf(alpha) <= 3.402823466e+38f) || !(fabsf(beta) <= 3.402823466e+38f)) return VTX_ERR_SHAPE;   // NaN, inf
+  const int kblocks = (Lk + AM_KB - 1) / AM_KB;
+  if ((int64_t)B * nH * kblocks >= 0x7fffffffLL) return VTX_ERR_SHAPE;
+  if (!am_aligned(q, 15) || !am_aligned(k, 15) || !am_aligned(w, 3) || !am_aligned(out_heads, 3) || !am_aligned(out_mix, 3) ||
+      !am_aligned(ws, 3))
+    return VTX_ERR_ALIGN;
+  if (!ws || ws_bytes < vtx_attn_map_colsum_workspace_bytes(B, Lq, Lk, nH, R)) return VTX_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  float* ml = (float*)ws;
+  float* c = out_heads ? out_heads : ml + (size_t)2 * B * nH * Lq;
+  rc = AM_DISPATCH(am_ml_t, q, k, ml, B, g, st);
+  if (rc) return rc;
+  rc = AM_DISPATCH(am_colsum_t, q, k, ml, w, c, B, R, kblocks, g, st);
+  if (rc || !out_mix) return rc;
+  const int64_t n = (int64_t)B * R * Lk;
+  hipLaunchKernelGGL(attn_map_mix_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c, w, out_mix, alpha, beta, n, nH, R, Lk);
+  return vtx_check_launch();
 }
 
 /* include/vtx.h: vtx_attn_map_meter */

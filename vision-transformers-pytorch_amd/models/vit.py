@@ -185,6 +185,12 @@ class VisionTransformer(nn.Module):
         from vtx.attnmap import cls_attention_maps
         return cls_attention_maps(self, input, layer)
 
+    def attention_rollout(self, input, residual=0.5, start_layer=0):
+        """The CLS row of the attention rollout from ``start_layer`` on, over the patch grid, as (B, gh, gw) float32:
+        vtx.attnmap.cls_rollout_maps."""
+        from vtx.attnmap import cls_rollout_maps
+        return cls_rollout_maps(self, input, residual, start_layer)
+
     def interpolate_pos_embedding(self, input, pos_embed):
         """Reference call style (vit.py:153-175): ``input`` is the (batch, 1 + n_patch, dim) token tensor."""
         return resize_position_grid(pos_embed, input.shape[1] - 1)

@@ -17,7 +17,8 @@
                   mass_mask, cls_attention_maps, AttentionStatsMeter, attention_statistics (also reachable as
                   vtx.attention_rows, ...); for window and halo attention (Swin, Twins, Halo): window_attention_rows,
                   window_attention_stats, halo_attention_rows, halo_attention_stats, WindowAttentionStatsMeter,
-                  window_attention_map
+                  window_attention_map; weighted column sums of P and attention rollout: attention_colsum,
+                  attention_received, attention_rollout, cls_rollout_maps
 """
 
 _KNN_NAMES = ("FeatureBank", "KnnMeter", "knn_search", "extract_features", "knn_evaluate", "ShardedFeatureBank",
@@ -25,7 +26,8 @@ _KNN_NAMES = ("FeatureBank", "KnnMeter", "knn_search", "extract_features", "knn_
 _PROBE_NAMES = ("LinearProbe", "ProbeMeter", "linear_probe_evaluate")
 _ATTNMAP_NAMES = ("attention_rows", "attention_stats", "mass_mask", "cls_attention_maps", "AttentionStatsMeter",
                   "attention_statistics", "window_attention_rows", "window_attention_stats", "halo_attention_rows",
-                  "halo_attention_stats", "WindowAttentionStatsMeter", "window_attention_map")
+                  "halo_attention_stats", "WindowAttentionStatsMeter", "window_attention_map", "attention_colsum",
+                  "attention_received", "attention_rollout", "cls_rollout_maps")
 
 
 def __getattr__(name):

@@ -11,6 +11,11 @@ package's own kernels: rows of P on request, the statistics in one streaming pas
   cls_attention_maps                               DINO's get_last_selfattention(x)[:, :, 0, 1:] as (B, nH, gh, gw)
   AttentionStatsMeter, attention_statistics        per (layer, head) means over batches, one host synchronisation
 
+Weighted column sums of P (vtx_attn_map_colsum: no P, no L x L product):
+
+  attention_colsum / attention_received            c = sum_i w_i p_ij per head; the mean attention a key receives
+  attention_rollout / cls_rollout_maps             rollout rows of a model from its taps, one blend call per layer
+
 Window and halo attention (Swin, the Twins locally-grouped half, Halo; reference swin_transformer.py:103-160) -- the same kernels
 with the relative-position bias, the shifted-window mask and the window addressing of vtx_attn_hdw_fwd:
 
@@ -75,6 +80,40 @@ def mass_mask(maps, keep=0.6):
     return ops.attn_mass_mask(maps.contiguous(), keep)
 
 
+MAX_WEIGHT_ROWS = 16             # weight rows of one vtx_attn_map_colsum call (AM_RMAX)
+
+
+def _weights(weights, q):
+    """``weights`` as the kernel takes it: float32 [B, R <= 16, Lq] on the device, contiguous."""
+    if not torch.is_tensor(weights) or weights.dim() != 3 or weights.dtype != torch.float32:
+        raise VtxError("vtx: attention_colsum takes float32 weights [B, R, Lq]")
+    if torch.is_tensor(q) and q.dim() == 3 and (weights.shape[0] != q.shape[0] or weights.shape[2] != q.shape[1]):
+        raise VtxError(f"vtx: attention_colsum: weights {tuple(weights.shape)} for {q.shape[0]} images of {q.shape[1]} queries")
+    if not 1 <= weights.shape[1] <= MAX_WEIGHT_ROWS:
+        raise VtxError(f"vtx: attention_colsum takes 1..{MAX_WEIGHT_ROWS} weight rows per call, got {weights.shape[1]}: loop over chunks")
+    if not weights.is_cuda:
+        raise VtxError("vtx: attention_colsum needs its weights on the device (there is no CPU fallback)")
+    return weights.contiguous()
+
+
+def attention_colsum(qkv_or_q, k=None, *, n_head, weights):
+    """Weighted column sums of P = softmax(q k^T / sqrt(D)): c[b, h, r, j] = sum_i weights[b, r, i] p[b, h, i, j], fp32
+    [B, nH, R, Lk], for float32 device ``weights`` [B, R, Lq] shared by the heads (R <= 16; any finite values).  P is never
+    written; a one-hot row returns the bits of that row of ``attention_rows``."""
+    w = _weights(weights, qkv_or_q)
+    q, kk = _operands(qkv_or_q, k, n_head)
+    return ops.attn_map_colsum(q, kk, n_head, w, heads=True)[0]
+
+
+def attention_received(qkv_or_q, k=None, *, n_head):
+    """The mean over the queries of the attention each key receives, fp32 [B, nH, Lk]: ``attention_colsum`` with every
+    weight the float32 1 / Lq, built on the device.  Each head's values sum to 1 over the keys."""
+    q, kk = _operands(qkv_or_q, k, n_head)
+    B, Lq = q.shape[0], q.shape[1]
+    w = torch.full((B, 1, Lq), 1.0 / Lq, dtype=torch.float32, device=q.device)
+    return ops.attn_map_colsum(q, kk, n_head, w, heads=True)[0][:, :, 0]
+
+
 # ------------------------------------------------------------------------------------------------ models
 def _vit_layers(model):
     layers = getattr(model, "layers", None)
@@ -94,6 +133,61 @@ def cls_attention_maps(model, images, layer=-1):
     nH = model.layers[0].attn.n_head
     p, _ = attention_rows(qkv, n_head=nH, row0=0, nrows=1)
     return p[:, :, 0, 1:].reshape(p.shape[0], nH, gh, gw)
+
+
+def rollout_coefficients(residual, n_head):
+    """(alpha, beta) of one rollout step w <- alpha w + beta sum_h (w^T P_h): alpha = fp32(residual), beta =
+    fp32((1 - residual) / n_head) -- the subtraction and the division in double on the host, each rounded to fp32 once
+    (returned as the Python floats of those fp32 values)."""
+    r = float(residual)
+    return (float(torch.tensor(r, dtype=torch.float64).to(torch.float32)),
+            float(torch.tensor((1.0 - r) / int(n_head), dtype=torch.float64).to(torch.float32)))
+
+
+def _rollout(model, images, rows, residual, start_layer):
+    mods = _vit_layers(model)
+    depth, nH = len(mods), mods[0].attn.n_head
+    r = float(residual)
+    if not 0.0 <= r < 1.0:                                  # (a NaN fails both comparisons)
+        raise VtxError(f"vtx: attention_rollout: residual {residual} outside [0, 1)")
+    if not -depth <= int(start_layer) < depth:
+        raise VtxError(f"vtx: attention_rollout: start_layer {start_layer} of a model of {depth} layers")
+    start = int(start_layer) % depth
+    rows = [int(i) for i in rows]
+    if not 1 <= len(rows) <= MAX_WEIGHT_ROWS:
+        raise VtxError(f"vtx: attention_rollout takes 1..{MAX_WEIGHT_ROWS} rows per call, got {len(rows)}: loop over chunks of rows")
+    if torch.is_tensor(images) and images.dim() == 4:
+        patch = model.patch_embedding.linear.kernel_size
+        L = 1 + (images.shape[2] // patch[0]) * (images.shape[3] // patch[1])
+        if any(not 0 <= i < L for i in rows):
+            raise VtxError(f"vtx: attention_rollout: rows {rows} outside [0, {L}) tokens")
+    taps, _, grid = model.attention_inputs(images, layers=tuple(range(start, depth)))      # refuses everything else
+    B, L = taps[start].shape[0], taps[start].shape[1]
+    alpha, beta = rollout_coefficients(r, nH)
+    w = torch.zeros((B, len(rows), L), dtype=torch.float32, device=taps[start].device)
+    w[:, torch.arange(len(rows), device=w.device), torch.tensor(rows, device=w.device)] = 1.0
+    nxt = torch.empty_like(w)
+    for l in range(depth - 1, start - 1, -1):               # the row vector meets the last layer first
+        q, kk = _operands(taps[l], None, nH)
+        ops.attn_map_colsum(q, kk, nH, w, heads=False, mix=(alpha, beta), out_mix=nxt)
+        w, nxt = nxt, w
+    return w, grid
+
+
+def attention_rollout(model, images, rows=(0,), residual=0.5, start_layer=0):
+    """Attention rollout (Abnar & Zuidema) of a models.vit.VisionTransformer for the query tokens ``rows``: row i of
+    A_depth-1 ... A_start with A_l = residual I + (1 - residual) mean_h P_l, as fp32 [B, len(rows), L].  Every layer from
+    ``start_layer`` on is tapped by ``model.attention_inputs``; the one-hot rows are pushed through the layers from the
+    last down to ``start_layer``, one ``out_mix`` call of vtx_attn_map_colsum each: w <- alpha w + beta sum_h (w^T P_h)
+    with (alpha, beta) = ``rollout_coefficients``.  No P and no L x L product is ever formed, and nothing is
+    renormalised: the rows of A_l sum to 1 analytically.  At most 16 rows per call."""
+    return _rollout(model, images, rows, residual, start_layer)[0]
+
+
+def cls_rollout_maps(model, images, residual=0.5, start_layer=0):
+    """Row 0 of ``attention_rollout`` without the CLS column, on the patch grid: fp32 (B, gh, gw)."""
+    w, (gh, gw) = _rollout(model, images, (0,), residual, start_layer)
+    return w[:, 0, 1:].reshape(w.shape[0], gh, gw)
 
 
 class AttentionStatsMeter:

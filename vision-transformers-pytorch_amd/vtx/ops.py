@@ -1597,6 +1597,40 @@ def attn_map_stats(q, k, n_head, n_prefix=1, grid=None):
     return stats
 
 
+def attn_map_colsum(q, k, n_head, w, heads=True, mix=None, out_mix=None):
+    """Weighted column sums of P = softmax(q k^T / sqrt(D)) without writing P: c[b, h, r, j] = sum_i w[b, r, i] p[b, h, i, j] for the
+    fp32 device weights ``w`` [B, R, Lq], R <= 16.  ``q`` / ``k`` are views as in attn_map_rows.  ``heads``: return c as fp32
+    [B, nH, R, Lk]; ``mix`` = (alpha, beta), Lq == Lk: also alpha * w + beta * sum_h c as fp32 [B, R, Lk] (into ``out_mix`` if given).
+    -> (c or None, mix or None); order of every sum, bit rules and refusals: include/vtx.h."""
+    B, Lq, Lk, D, ldq, ldkv = _attn_map_operands(q, k, n_head, "attn_map_colsum")
+    nH = int(n_head)
+    if not torch.is_tensor(w) or not w.is_cuda or w.device != q.device:
+        raise VtxError("vtx: attn_map_colsum needs its weights on the operands' device (there is no CPU fallback)")
+    if w.dtype != torch.float32 or w.dim() != 3 or w.shape[0] != B or w.shape[2] != Lq or not w.is_contiguous():
+        raise VtxError(f"vtx: attn_map_colsum takes contiguous float32 weights [B = {B}, R, Lq = {Lq}], got {tuple(w.shape)} {w.dtype}")
+    R = w.shape[1]
+    if not 1 <= R <= 16:
+        raise VtxError(f"vtx: attn_map_colsum takes 1..16 weight rows per call, got {R}: loop over chunks of rows")
+    if not heads and mix is None:
+        raise VtxError("vtx: attn_map_colsum: neither the per-head sums nor the blend is asked for")
+    alpha = beta = 0.0
+    if mix is not None:
+        alpha, beta = float(mix[0]), float(mix[1])
+        if Lq != Lk:
+            raise VtxError(f"vtx: attn_map_colsum: the blend needs Lq == Lk, got {Lq} and {Lk}")
+        if out_mix is None:
+            out_mix = torch.empty((B, R, Lk), dtype=torch.float32, device=q.device)
+        elif out_mix.shape != (B, R, Lk) or out_mix.dtype != torch.float32 or not out_mix.is_contiguous() or out_mix.device != q.device:
+            raise VtxError(f"vtx: attn_map_colsum: out_mix is a contiguous float32 device tensor [{B}, {R}, {Lk}]")
+    c = torch.empty((B, nH, R, Lk), dtype=torch.float32, device=q.device) if heads else None
+    lib = _lib.load()
+    nws = int(lib.vtx_attn_map_colsum_workspace_bytes(B, Lq, Lk, nH, R))
+    ws = torch.empty(max(nws, 4), dtype=torch.uint8, device=q.device)
+    check(lib.vtx_attn_map_colsum(_p(q), _p(k), ldq, ldkv, _p(w), _p(c), _p(out_mix) if mix is not None else None, alpha, beta, B, Lq, Lk,
+                                  nH, D, R, _p(ws), nws, _dt(q), _stream()), "vtx_attn_map_colsum")
+    return c, (out_mix if mix is not None else None)
+
+
 def attn_mapw_rows(q, kv, B, Lq, Lk, n_head, D, swin=None, bias=None, mask=None, row0=0, nrows=1):
     """Rows row0 .. row0 + nrows - 1 of softmax(q k^T / sqrt(D) + bias, masked cells excluded) of every problem and head of a window /
     halo attention; operands and checks as attn_hdw_fwd: swin = (H, W, win, shift) with q the packed QKV projection of B images in
