@@ -1127,6 +1127,63 @@ int vtx_attn_map_colsum(const void* q, const void* k, int64_t ldq, int64_t ldkv,
                         float alpha, float beta, int B, int Lq, int Lk, int nH, int D, int R, void* ws, size_t ws_bytes, int dtype,
                         void* stream);
 
+/* ---- Label propagation for semi-supervised video object segmentation on frozen patch tokens (csrc/labelprop.hip,
+ * csrc/knn_select.h): the DAVIS protocol of the DINO paper.  The search is vtx_knn_topk restricted to a spatial
+ * neighbourhood by address arithmetic; no affinity matrix of n_ctx P x P exists and no score outside the neighbourhoods is
+ * formed.  No host synchronisation, no floating-point atomics: the same inputs give the same bits.
+ *
+ * Geometry: B independent sequences on a patch grid h x w; token p = y * w + x, P = h w; feature width D.
+ *
+ * vtx_labelprop_topk: tar [B, P, D] the target frame, ctx [B, S, P, D] a ring of S frame slots, both dtype (bf16 / fp32);
+ *   rows are used as given -- nothing is normalised here.  slots: HOST array of n_ctx (1..16) slot numbers in 0..S-1, copied
+ *   into the launch by value (no device copy, no synchronisation: rotating the queue is free); a slot may repeat.
+ *   - Candidates.  Key (c, p') is token p' of slot slots[c]; its index is c * P + p'.  It is a candidate for query (y, x)
+ *     exactly when |y - y'| <= radius and |x - x'| <= radius: a Chebyshev box clipped at the grid border, with no wrap from
+ *     one grid row into the next.  radius >= max(h, w) - 1 restricts nothing.
+ *   - val [B, P, k] fp32, idx [B, P, k] int32: the first k candidates in the total order of vtx_knn_topk -- higher score
+ *     first, among equal scores the lower index first -- listed in that order.  A query with fewer than k candidates ends
+ *     its list with the sentinels (-inf, 0x7fffffff).
+ *   - Exactly k under a total order.  The usual torch composition (dense exp(f_tar . f_ctx / T), a box mask, topk, a
+ *     threshold at the k-th largest weight) keeps EVERY key whose weight is >= the k-th largest; this entry keeps exactly
+ *     k.  The two differ on exact ties at the k-th place, and only there.
+ *   - Pair-local scores.  The score of a pair is the fp32 result of ONE MFMA chain over D that depends on its two rows
+ *     only: v_mfma_f32_16x16x32_bf16 per 32 columns (bf16) or 8 x v_mfma_f32_16x16x4_f32 per 32 columns (fp32, exact
+ *     products), chunks ascending from 0.f -- the chain of vtx_knn_topk, so a pair's val is bit for bit what vtx_knn_topk
+ *     returns for the same two rows.  A query's list does not depend on B, on how the batch is cut into calls, or on
+ *     which tile the query falls in.
+ *   - A NaN score orders as -inf.  Every written index is a real candidate index or the sentinel, and the call ends.
+ *   Errors, all before any launch, with the codes of the k-NN entries: VTX_ERR_NULL (tar, ctx, slots, val, idx),
+ *   VTX_ERR_SHAPE (B, h, w < 1; n_ctx outside 1..16; a slot outside 0..S-1; D > 1024; k outside 1..64; radius < 0;
+ *   n_ctx * P >= 2^31 - 1; B * S * P >= 2^31), VTX_ERR_DTYPE, VTX_ERR_ALIGN (D % 8 != 0; tar or ctx not 16-byte aligned; val
+ *   or idx off 4).
+ *
+ * vtx_labelprop_vote: val / idx [B, P, k] (a search result), seg [B, S, P, C] fp32 the soft labels of the ring, channels
+ *   last, slots / n_ctx / S as above, out [B, P, C] fp32, temperature T.  Per query, i over the k places in order:
+ *     d_i    = val_i - val_0              one fp32 subtraction; val_0 = the list's first score, its largest; d_i = 0 where
+ *                                         val_i == val_0 (so that -inf - -inf is not formed)
+ *     w_i    = expf(d_i / T)              one fp32 division, expf; w_0 = 1 and no w_i can overflow.  After the
+ *                                         normalisation below this is the composition's exp(val_i / T).
+ *     num[c] = sum_i (w_i * seg[key_i][c])   each product one fp32 multiply rounded on its own, added in neighbour order
+ *     den    = sum_i w_i                     added in neighbour order
+ *     out[c] = num[c] / den               one IEEE fp32 division; 0 where no place counts
+ *   Products and sums are never contracted into an fma.  key_i = (slot slots[idx_i / P], token idx_i % P).  A sentinel place
+ *   is skipped: it adds to neither sum.  So is any other index outside [0, n_ctx P): it is refused by nothing on the device,
+ *   it is skipped and never dereferenced.
+ *   Errors, all before any launch: VTX_ERR_NULL (any pointer), VTX_ERR_SHAPE (C outside 1..1024; k outside 1..64; T not > 0
+ *   or not finite; B, P < 1; n_ctx outside 1..16; a slot outside 0..S-1; n_ctx * P >= 2^31 - 1; B * S * P >= 2^31),
+ *   VTX_ERR_ALIGN (a pointer off 4).
+ *
+ * vtx_mask_overlap: pred, gt [N, P] int32 label maps; counts [N, C, 3] int64 = per map and per label c in [0, C):
+ *   [#(pred == c & gt == c), #(pred == c), #(gt == c)].  Labels outside [0, C) count for nothing.  Integer, fixed order, no
+ *   atomics; counts is overwritten.  The region similarity J of a label is inter / (|pred| + |gt| - inter).
+ *   Errors, all before any launch: VTX_ERR_NULL, VTX_ERR_SHAPE (N, P, C < 1; C > 256; N * P >= 2^31), VTX_ERR_ALIGN (pred or
+ *   gt off 4, counts off 8). */
+int vtx_labelprop_topk(const void* tar, const void* ctx, const int32_t* slots, int n_ctx, int S, float* val, int32_t* idx,
+                       int64_t B, int h, int w, int D, int radius, int k, int dtype, void* stream);
+int vtx_labelprop_vote(const float* val, const int32_t* idx, const float* seg, const int32_t* slots, int n_ctx, int S,
+                       float* out, int64_t B, int64_t P, int k, int C, float T, void* stream);
+int vtx_mask_overlap(const int32_t* pred, const int32_t* gt, int64_t* counts, int64_t N, int64_t P, int C, void* stream);
+
 /* ---- Multi-tensor weight cast (csrc/cast.hip): all fp32 Linear / Conv weights of a model -> bf16, plain [out][in]
  * and transposed [in][out], in one launch per forward.  This is the per-call weight cast of the reference's bf16
  * autocast (torch.cuda.amp.autocast around model(input), train.py:273-274) done once for the whole model.

@@ -180,6 +180,35 @@ class VisionTransformer(nn.Module):
                     tokens = layer(tokens)
             return taps, self.norm(tokens[:, 0]), grid
 
+    def patch_tokens(self, input):
+        """The normalised patch tokens ``self.norm(tokens)[:, 1:]`` as (B, P, dim) plus the patch grid (gh, gw): the frozen
+        features ``vtx.vos`` propagates labels on (forward_feature keeps the CLS row only).  Needs ``eval()``,
+        ``torch.no_grad()`` and ONE image tensor on the device.  The forward is forward_feature's own, piece by piece;
+        ``forward`` and ``forward_feature`` are untouched.  Square inputs only: the position table's resize is square in
+        this package and in the reference (vit.py:153-175)."""
+        from vtx.ops import VtxError
+        if isinstance(input, (list, tuple)) or not torch.is_tensor(input) or input.dim() != 4:
+            raise VtxError("vtx: patch_tokens takes one (B, 3, H, W) image tensor, not a list of crops")
+        if self.training:
+            raise VtxError("vtx: patch_tokens needs model.eval(): features under dropout / DropPath are not frozen features")
+        if torch.is_grad_enabled():
+            raise VtxError("vtx: patch_tokens runs under torch.no_grad(): its output has no gradient")
+        if input.shape[2] != input.shape[3]:
+            raise VtxError(f"vtx: patch_tokens takes square images (the position table's resize is square), got "
+                           f"{input.shape[2]} x {input.shape[3]}")
+        if not input.is_cuda:
+            raise VtxError("vtx: patch_tokens needs device tensors (there is no CPU fallback)")
+        patch = self.patch_embedding.linear.kernel_size
+        grid = (input.shape[2] // patch[0], input.shape[3] // patch[1])
+        with VF.weight_scope(self, input):
+            tokens = self.patch_embedding(input)
+            tokens = VF.VitAssembleFn.apply(tokens, self.cls_token, resize_position_grid(self.pos_embed, tokens.shape[1]))
+            tokens = self.pos_drop(tokens)
+            with drop_path_scope(self, tokens.shape[0], tokens.device):
+                for layer in self.layers:
+                    tokens = layer(tokens)
+            return self.norm(tokens)[:, 1:], grid
+
     def attention_maps(self, input, layer=-1):
         """DINO's CLS self-attention maps of ``layer`` as (B, heads, gh, gw) float32: vtx.attnmap.cls_attention_maps."""
         from vtx.attnmap import cls_attention_maps

@@ -19,8 +19,12 @@
                   window_attention_stats, halo_attention_rows, halo_attention_stats, WindowAttentionStatsMeter,
                   window_attention_map; weighted column sums of P and attention rollout: attention_colsum,
                   attention_received, attention_rollout, cls_rollout_maps
+  vtx.vos         label propagation for semi-supervised video object segmentation on frozen patch tokens (the DAVIS
+                  protocol of DINO): labelprop_topk, labelprop_vote, LabelPropagator, propagate_video, region_similarity
+                  (also reachable as vtx.LabelPropagator, ...)
 """
 
+_VOS_NAMES = ("labelprop_topk", "labelprop_vote", "LabelPropagator", "propagate_video", "region_similarity")
 _KNN_NAMES = ("FeatureBank", "KnnMeter", "knn_search", "extract_features", "knn_evaluate", "ShardedFeatureBank",
               "knn_search_sharded")
 _PROBE_NAMES = ("LinearProbe", "ProbeMeter", "linear_probe_evaluate")
@@ -45,4 +49,7 @@ def __getattr__(name):
     if name in _ATTNMAP_NAMES:
         from . import attnmap
         return getattr(attnmap, name)
+    if name in _VOS_NAMES:
+        from . import vos
+        return getattr(vos, name)
     raise AttributeError(f"module 'vtx' has no attribute {name!r}")

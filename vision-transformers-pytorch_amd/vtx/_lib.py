@@ -306,6 +306,11 @@ _SIGNATURES = {
                              c_int64, c_int, c_int64, c_int, c_float, c_void_p]),
     "vtx_knn_merge_lists": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
                                     c_int64, c_int64, c_int64, c_void_p]),
+    "vtx_labelprop_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                   c_int, c_int, c_int, c_void_p]),
+    "vtx_labelprop_vote": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int,
+                                   c_int, c_float, c_void_p]),
+    "vtx_mask_overlap": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "vtx_probe_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
     "vtx_probe_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p]),

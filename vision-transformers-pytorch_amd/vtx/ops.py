@@ -1551,6 +1551,74 @@ def knn_vote(val, idx, bank_labels, query_labels, ks, n_class, T, meter=None):
     return rank, pred
 
 
+# ------------------------------------------------------------------------------- label propagation (csrc/labelprop.hip)
+def _slot_array(slots):
+    return slots if isinstance(slots, ctypes.Array) else (ctypes.c_int32 * len(slots))(*[int(s) for s in slots])
+
+
+def _into(out, shape, dtype, device, what):
+    """``out`` checked against (shape, dtype), or a new tensor."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _dev(out)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype:
+        raise VtxError(f"vtx: {what} must be a {dtype} tensor of shape {tuple(shape)}")
+    return out
+
+
+def labelprop_topk(tar, ctx, slots, h, w, radius, k, out=None):
+    """The k best context tokens of every target token inside its spatial neighbourhood: ``tar`` [B, P, D], ``ctx``
+    [B, S, P, D] (a ring of S frame slots), both float32 or both bfloat16, P = h w; ``slots`` host ints (or a prepared
+    ``ctypes.c_int32`` array) naming the n_ctx slots that take part, in index order.  ``out`` = (val, idx) to write into.
+    -> (val fp32 [B, P, k], idx int32 [B, P, k]); rules and limits: include/vtx.h."""
+    _dev(tar, ctx)
+    if tar.dim() != 3 or ctx.dim() != 4 or tar.dtype != ctx.dtype or ctx.shape[0] != tar.shape[0] \
+            or tuple(ctx.shape[2:]) != tuple(tar.shape[1:]) or tar.shape[1] != int(h) * int(w):
+        raise VtxError(f"vtx: labelprop_topk takes a [B, P, D] target and a [B, S, P, D] ring of one dtype with P = h w, got "
+                       f"{tuple(tar.shape)} {tar.dtype} / {tuple(ctx.shape)} {ctx.dtype} on a {h} x {w} grid")
+    B, P, D = tar.shape
+    S, k = ctx.shape[1], int(k)
+    sl = _slot_array(slots)
+    val = _into(None if out is None else out[0], (B, P, max(k, 0)), torch.float32, tar.device, "val")
+    idx = _into(None if out is None else out[1], (B, P, max(k, 0)), torch.int32, tar.device, "idx")
+    with _timed("labelprop_search_kernel", 0.0, 0.0):
+        check(_lib.load().vtx_labelprop_topk(_p(tar), _p(ctx), sl, len(sl), S, _p(val), _p(idx), B, int(h), int(w), D,
+                                             int(radius), k, _dt(tar), _stream()), "vtx_labelprop_topk")
+    return val, idx
+
+
+def labelprop_vote(val, idx, seg, slots, T, out=None):
+    """Soft labels of the queries from a labelprop_topk result: ``seg`` fp32 [B, S, P, C], weights
+    expf((val - val[..., :1]) / T), sums in neighbour order, sentinel and out-of-range places skipped.
+    -> out fp32 [B, P, C]; rules: include/vtx.h."""
+    _dev(val, idx, seg)
+    if val.dim() != 3 or val.shape != idx.shape or val.dtype != torch.float32 or idx.dtype != torch.int32:
+        raise VtxError("vtx: labelprop_vote takes the (val fp32, idx int32) pair of labelprop_topk")
+    if seg.dim() != 4 or seg.dtype != torch.float32 or seg.shape[0] != val.shape[0] or seg.shape[2] != val.shape[1]:
+        raise VtxError(f"vtx: labelprop_vote takes float32 soft labels [B, S, P, C] for lists {tuple(val.shape)}, got "
+                       f"{tuple(seg.shape)} {seg.dtype}")
+    B, P, k = val.shape
+    S, C = seg.shape[1], seg.shape[3]
+    sl = _slot_array(slots)
+    o = _into(out, (B, P, C), torch.float32, val.device, "out")
+    with _timed("labelprop_vote_kernel", 0.0, 0.0):
+        check(_lib.load().vtx_labelprop_vote(_p(val), _p(idx), _p(seg), sl, len(sl), S, _p(o), B, P, k, C, float(T),
+                                             _stream()), "vtx_labelprop_vote")
+    return o
+
+
+def mask_overlap(pred, gt, n_label, out=None):
+    """counts int64 [N, n_label, 3] = per map and label [#(pred == c & gt == c), #(pred == c), #(gt == c)] of int32 label
+    maps ``pred`` / ``gt`` [N, P]; labels outside [0, n_label) count for nothing."""
+    _dev(pred, gt)
+    if pred.dim() != 2 or pred.shape != gt.shape or pred.dtype != torch.int32 or gt.dtype != torch.int32:
+        raise VtxError("vtx: mask_overlap takes two int32 label maps of one [N, P] shape")
+    N, P = pred.shape
+    counts = _into(out, (N, max(int(n_label), 0), 3), torch.int64, pred.device, "counts")
+    check(_lib.load().vtx_mask_overlap(_p(pred), _p(gt), _p(counts), N, P, int(n_label), _stream()), "vtx_mask_overlap")
+    return counts
+
+
 # ------------------------------------------------------------------------------- attention maps (csrc/attention_maps.hip)
 def _attn_map_operands(q, k, n_head, what):
     """(B, Lq, Lk, D, ldq, ldkv) of a query view (B, Lq, >= nH D) and a key view (B, Lk, >= nH D) whose first nH * D columns are
