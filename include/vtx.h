@@ -44,7 +44,9 @@ extern "C" {
 #define VTX_ERR_JPEG (-7)      /* not a supported JPEG (the reason is in VtxJpegInfo.reason), or an invalid decode plan */
 
 const char* vtx_strerror(int code);
-/* ABI version of the library (bumped on any signature change). */
+/* ABI version of the library (bumped on any signature change): what this header declares, and what vtx_abi_version() of a
+ * library compiled against it returns.  vtx/_lib.py binds the library from this file and refuses one of another version. */
+#define VTX_ABI_VERSION 30
 int vtx_abi_version(void);
 /* Compute units of the current device (256 on MI355X; 256 when no device can be asked): what the one-workgroup-per-CU kernels size their
  * grids and the dispatch heuristics their thresholds with.  The heuristics themselves live in the library only: the bindings ask
@@ -333,7 +335,8 @@ int vtx_wattn_bwd(const void* qkv, const void* o, const void* dout, const float*
  * (C, ff), (ff, C), (C, C), (3C, C)) are workspaces; dW? / db? / dg? / dbe? (/ drel) receive the parameter gradients (fp32).
  * `side_stream` != NULL sends the grouped weight gradient + its reduce there behind an event fork; the caller joins.
  * accumulate: as for vtx_wgrad_group. */
-enum { VTX_ATTN_WINDOW = 1, VTX_ATTN_GLOBAL = 2 };
+#define VTX_ATTN_WINDOW 1
+#define VTX_ATTN_GLOBAL 2
 typedef struct VtxLayerFwd {
   int dtype, attn_kind;
   int64_t M;                                   /* tokens */

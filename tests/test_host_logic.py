@@ -49,12 +49,16 @@ def test_library_exports_every_declared_symbol():
     from vtx import _lib
     lib = _lib.load()
     header = open(os.path.join(REPO, "include", "vtx.h")).read()
+    # the text the binding's reader sees: comments name entries too ("vtx_wattn_bwd_parts() partial rows", "vtx_layer_desc_bytes(4 / 5)")
+    header = re.sub(r"/\*.*?\*/|//[^\n]*", " ", header, flags=re.S)
     declared = sorted(set(re.findall(r"\b(vtx_[a-z0-9_]+)\s*\(", header)))
     assert declared, "no declarations found in include/vtx.h"
     for name in declared:
         assert hasattr(lib, name), f"libvtx.so does not export {name}"
     assert sorted(_lib.exported_symbols()) == declared, "ctypes binding and include/vtx.h disagree"
     assert lib.vtx_abi_version() == _lib.ABI_VERSION
+    abi = re.search(r"^#define\s+VTX_ABI_VERSION\s+(\d+)\s*$", header, re.M)
+    assert abi and lib.vtx_abi_version() == int(abi.group(1)) == _lib.read_header(header)[2]["VTX_ABI_VERSION"]
     assert b"multiple of 8" in lib.vtx_strerror(-3)
 
 

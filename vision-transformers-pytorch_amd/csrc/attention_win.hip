@@ -27,7 +27,6 @@
 
 #include "options.h"
 #include "vtx_common.h"
-#include "../../include/vtx.h"    // (VtxRoute; after the internal header, as in layer.hip)
 
 #define WA_D 32
 #define WA_LP 64

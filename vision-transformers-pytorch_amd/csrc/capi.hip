@@ -101,7 +101,7 @@ const char* vtx_strerror(int code) {
   }
 }
 
-int vtx_abi_version(void) { return 30; }
+int vtx_abi_version(void) { return VTX_ABI_VERSION; }
 
 int vtx_cu_count(void) { return vtx_cu_count_cached(); }
 

@@ -21,7 +21,6 @@
 // Workgroup ids are remapped so that tiles sharing an operand panel run on the same XCD (private L2).
 #include "gemm_common.h"
 #include "options.h"
-#include "../../include/vtx.h"    // (VtxRoute, VtxGemmQuery; after the internal header, as in layer.hip)
 
 template <typename T> struct GemmGeom {
   static constexpr int BK = 128 / (int)sizeof(T);      // elements per LDS k-tile row

@@ -13,7 +13,6 @@
 #include <vector>
 
 #include "gemm_common.h"
-#include "../../include/vtx.h"    // (after the internal header: its VTX_* macros shadow the internal enum of the same values)
 
 namespace {
 

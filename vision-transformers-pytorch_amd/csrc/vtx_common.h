@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/vtx.h"   // the C ABI: every translation unit compiles its extern "C" definitions against the prototypes
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -15,10 +16,6 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 #define VTX_WAVE 64
-
-enum { VTX_OK = 0, VTX_ERR_SHAPE = -1, VTX_ERR_DTYPE = -2, VTX_ERR_ALIGN = -3, VTX_ERR_LAUNCH = -4,
-       VTX_ERR_WORKSPACE = -5, VTX_ERR_NULL = -6, VTX_ERR_JPEG = -7 };
-enum { VTX_F32 = 0, VTX_BF16 = 1 };
 
 #ifndef VTX_PK_DS_GUARD
 #define VTX_PK_DS_GUARD 1          // see shfl_xor_f below
