@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/vtx.h"   // the C ABI: every translation unit compiles its extern "C" definitions against the prototypes
+#include "../../include/vtx_vos.h"   // the second public header (DAVIS J&F, csrc/davis.hip): the same guarantee
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;

@@ -21,10 +21,12 @@
                   attention_received, attention_rollout, cls_rollout_maps
   vtx.vos         label propagation for semi-supervised video object segmentation on frozen patch tokens (the DAVIS
                   protocol of DINO): labelprop_topk, labelprop_vote, LabelPropagator, propagate_video, region_similarity
-                  (also reachable as vtx.LabelPropagator, ...)
+                  (also reachable as vtx.LabelPropagator, ...); the DAVIS J&F evaluation on the device: labels_from_soft,
+                  boundary_counts, f_of_counts, boundary_measure, first_frame_labels, davis_jf
 """
 
-_VOS_NAMES = ("labelprop_topk", "labelprop_vote", "LabelPropagator", "propagate_video", "region_similarity")
+_VOS_NAMES = ("labelprop_topk", "labelprop_vote", "LabelPropagator", "propagate_video", "region_similarity", "labels_from_soft",
+              "boundary_counts", "f_of_counts", "boundary_measure", "first_frame_labels", "davis_jf")
 _KNN_NAMES = ("FeatureBank", "KnnMeter", "knn_search", "extract_features", "knn_evaluate", "ShardedFeatureBank",
               "knn_search_sharded")
 _PROBE_NAMES = ("LinearProbe", "ProbeMeter", "linear_probe_evaluate")

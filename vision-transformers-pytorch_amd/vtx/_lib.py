@@ -1,8 +1,10 @@
-"""ctypes binding of libvtx.so, derived from include/vtx.h at import.
+"""ctypes binding of libvtx.so, derived from include/vtx.h and include/vtx_vos.h at import.
 
 The C ABI is written down once, in include/vtx.h: every csrc/*.hip compiles its definitions against that header, and this
 module reads the same file -- prototypes, the public structs and the integer #defines -- instead of mirroring it.  Only the
 JPEG records of csrc/jpeg_host.h / csrc/jpeg_sync.h, which the public header does not declare, are typed by hand.
+include/vtx_vos.h (the DAVIS J&F entries of csrc/davis.hip) is read the same way into a table of its own, _VOS_SIGNATURES, with
+its own version: _SIGNATURES, exported_symbols() and ABI_VERSION remain what include/vtx.h states.
 
 The library is the product: there is NO fallback.  If libvtx.so is missing or a call returns a
 non-zero code this module raises -- it never routes to PyTorch ops or to the CPU oracle.
@@ -14,6 +16,7 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VTX_LIBVTX") or os.path.join(_HERE, "libvtx.so")   # (override: A/B of two builds on one box)
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "vtx.h")
+VOS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "vtx_vos.h")
 
 
 class VtxError(RuntimeError):
@@ -25,7 +28,7 @@ _SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "int64_t": ctypes.c_
             "uint16_t": ctypes.c_uint16}
 
 
-def _ctype(ctext, decl, ret=False):
+def _ctype(ctext, decl, ret=False, name="include/vtx.h"):
     """ctypes type of the C type ``ctext``: any pointer is c_void_p (callers pass integers, None and byref(...)), a returned
     ``const char*`` is c_char_p, the scalars of _SCALARS map to themselves; anything else raises, naming ``decl``."""
     words = " ".join(ctext.replace("*", " * ").split())
@@ -36,10 +39,10 @@ def _ctype(ctext, decl, ret=False):
             return ctypes.c_char_p
     elif words.replace("const ", "") in _SCALARS:
         return _SCALARS[words.replace("const ", "")]
-    raise VtxError(f"include/vtx.h: no ctypes type for '{ctext.strip()}' in '{' '.join(decl.split())}'")
+    raise VtxError(f"{name}: no ctypes type for '{ctext.strip()}' in '{' '.join(decl.split())}'")
 
 
-def _struct_fields(body, decl):
+def _struct_fields(body, decl, header="include/vtx.h"):
     """_fields_ of one struct body: ``type a, *b, c[96];`` per statement, several declarators allowed."""
     fields = []
     for stmt in filter(None, (s.strip() for s in body.split(";"))):
@@ -47,16 +50,17 @@ def _struct_fields(body, decl):
         for d in rest.split(","):
             m = re.fullmatch(r"\s*(\*?)\s*(\w+)\s*(?:\[(\d+)\])?\s*", d)
             if not m:
-                raise VtxError(f"include/vtx.h: cannot read the field '{' '.join(stmt.split())}' of {decl}")
+                raise VtxError(f"{header}: cannot read the field '{' '.join(stmt.split())}' of {decl}")
             star, name, dim = m.groups()
-            t = ctypes.c_char if (base, star, bool(dim)) == ("char", "", True) else _ctype(base + star, f"{decl}: {stmt}")
+            t = ctypes.c_char if (base, star, bool(dim)) == ("char", "", True) else _ctype(base + star, f"{decl}: {stmt}", name=header)
             fields.append((name, t * int(dim) if dim else t))
     return fields
 
 
-def read_header(text):
-    """The C ABI as include/vtx.h states it: (prototypes, structs, defines) =
-    ({name: (restype, [argtypes])}, {typedef name: _fields_}, {macro: int}).  A declaration that is not understood raises."""
+def read_header(text, name="include/vtx.h"):
+    """The C ABI as a public header states it: (prototypes, structs, defines) =
+    ({name: (restype, [argtypes])}, {typedef name: _fields_}, {macro: int}).  A declaration that is not understood raises,
+    naming the file ``name``."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", lambda m: " " + "\n" * m.group().count("\n"), text, flags=re.S)   # comments name entries too
     defines = {m.group(1): int(m.group(2)) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, re.M)}
     text = re.sub(r"^[ \t]*#[ \t]*ifdef[ \t]+__cplusplus\b.*?^[ \t]*#[ \t]*endif\b", "", text, flags=re.M | re.S)   # extern "C" { and }
@@ -64,7 +68,7 @@ def read_header(text):
     structs = {}
 
     def take_struct(m):
-        structs[m.group(2)] = _struct_fields(m.group(1), m.group(2))
+        structs[m.group(2)] = _struct_fields(m.group(1), m.group(2), name)
         return " "
     text = re.sub(r"\btypedef\s+struct\s+\w*\s*\{([^{}]*)\}\s*(\w+)\s*;", take_struct, text)
     text = re.sub(r"\benum\s*\w*\s*\{[^{}]*\}\s*;", " ", text)
@@ -72,10 +76,10 @@ def read_header(text):
     for stmt in filter(None, (s.strip() for s in text.split(";"))):
         m = re.fullmatch(r"([^()]*?)(\w+)\s*\(([^()]*)\)", stmt)
         if not m:
-            raise VtxError(f"include/vtx.h: not a prototype: '{' '.join(stmt.split())}'")
+            raise VtxError(f"{name}: not a prototype: '{' '.join(stmt.split())}'")
         params = [] if m.group(3).strip() in ("", "void") else m.group(3).split(",")
-        protos[m.group(2)] = (_ctype(m.group(1), stmt, ret=True),
-                              [_ctype(re.fullmatch(r"(.*?)\w*", p, re.S).group(1), stmt) for p in params])
+        protos[m.group(2)] = (_ctype(m.group(1), stmt, ret=True, name=name),
+                              [_ctype(re.fullmatch(r"(.*?)\w*", p, re.S).group(1), stmt, name=name) for p in params])
     return protos, structs, defines
 
 
@@ -89,6 +93,18 @@ except OSError as _e:
 # ATTN_WINDOW, ATTN_GLOBAL, Q_RESID .. Q_INPLACE
 globals().update({k[4:]: v for k, v in _DEFINES.items() if k.startswith("VTX_")})
 ABI_VERSION = _DEFINES["VTX_ABI_VERSION"]      # (named: load() compares the library against it)
+
+# the second public header: the DAVIS J&F entries (csrc/davis.hip).  Its prototypes are bound next to _SIGNATURES and its
+# VTX_VOS_* macros are exported as VOS_*; it declares no struct and no error code.
+try:
+    with open(VOS_HEADER_PATH) as _fh:
+        _VOS_SIGNATURES, _VOS_STRUCTS, _VOS_DEFINES = read_header(_fh.read(), "include/vtx_vos.h")
+except OSError as _e:
+    raise VtxError(f"{VOS_HEADER_PATH} not found: the binding of libvtx.so is read from the public headers") from _e
+if _VOS_STRUCTS or set(_VOS_SIGNATURES) & set(_SIGNATURES) or set(_VOS_DEFINES) & set(_DEFINES):
+    raise VtxError("include/vtx_vos.h declares a struct, or redeclares an entry or a macro of include/vtx.h")
+globals().update({k[4:]: v for k, v in _VOS_DEFINES.items() if k.startswith("VTX_VOS_")})
+VOS_ABI_VERSION = _VOS_DEFINES["VTX_VOS_ABI_VERSION"]
 
 
 class LayerFwd(ctypes.Structure):
@@ -160,7 +176,7 @@ def load():
             f"{LIB_PATH} not found: the HIP extension is the product path and has no fallback. "
             "Build it with `python -c 'import __graft_entry__ as g; g.build()'`.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_VOS_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -169,6 +185,9 @@ def load():
         fn.argtypes = args
     if lib.vtx_abi_version() != ABI_VERSION:
         raise VtxError(f"libvtx.so ABI {lib.vtx_abi_version()} != binding ABI {ABI_VERSION}: rebuild")
+    if lib.vtx_vos_abi_version() != VOS_ABI_VERSION:
+        raise VtxError(f"libvtx.so VOS ABI {lib.vtx_vos_abi_version()} != binding VOS ABI {VOS_ABI_VERSION} "
+                       "(include/vtx_vos.h): rebuild")
     if lib.vtx_layer_desc_bytes(0) != ctypes.sizeof(LayerFwd) or lib.vtx_layer_desc_bytes(1) != ctypes.sizeof(LayerBwd):
         raise VtxError("libvtx.so layer descriptors do not match the bindings (VtxLayerFwd / VtxLayerBwd): rebuild")
     if lib.vtx_layer_desc_bytes(2) != ctypes.sizeof(SrLayerFwd) or lib.vtx_layer_desc_bytes(3) != ctypes.sizeof(SrLayerBwd):

@@ -11,7 +11,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "csrc")
-PUBLIC_HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "vtx.h")   # csrc/vtx_common.h includes it
+_INCLUDE = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include")
+PUBLIC_HEADERS = [os.path.join(_INCLUDE, "vtx.h"), os.path.join(_INCLUDE, "vtx_vos.h")]   # csrc/vtx_common.h includes both
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libvtx.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -41,7 +42,7 @@ def hipcc_version():
 def _stamp(src):
     h = hashlib.sha1()
     h.update(hipcc_version().encode())
-    for f in [src] + sorted(x for x in os.listdir(CSRC) if x.endswith(".h")) + [PUBLIC_HEADER]:
+    for f in [src] + sorted(x for x in os.listdir(CSRC) if x.endswith(".h")) + PUBLIC_HEADERS:
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(fh.read())
     h.update(" ".join(FLAGS).encode())

@@ -1619,6 +1619,45 @@ def mask_overlap(pred, gt, n_label, out=None):
     return counts
 
 
+# ------------------------------------------------------------------------------- DAVIS J&F (csrc/davis.hip, include/vtx_vos.h)
+def seg_labels(seg, scale, oh=0, ow=0, normalize=True, out=None):
+    """labels int32 [N, oh, ow] of fp32 soft labels ``seg`` [N, C, gh, gw]: bilinear upsample by the integer ``scale``,
+    per-channel min-max normalisation over the upsampled map, argmax, nearest resize to (oh, ow) (0, 0: the upsampled
+    size); rules and limits: include/vtx_vos.h."""
+    _dev(seg)
+    if seg.dim() != 4 or seg.dtype != torch.float32:
+        raise VtxError("vtx: seg_labels takes float32 soft labels [N, C, gh, gw]")
+    N, C, gh, gw = seg.shape
+    scale, oh, ow = int(scale), int(oh), int(ow)
+    shape = (N, oh, ow) if oh > 0 and ow > 0 else (N, gh * max(scale, 0), gw * max(scale, 0))
+    labels = _into(out, shape, torch.int32, seg.device, "labels")
+    lib = _lib.load()
+    ws, nbytes = None, 0
+    if normalize:
+        nbytes = lib.vtx_seg_labels_workspace(N, C)
+        ws = torch.empty((max(nbytes, 4),), dtype=torch.uint8, device=seg.device)
+    check(lib.vtx_seg_labels(_p(seg), _p(labels), N, C, gh, gw, scale, oh, ow, 1 if normalize else 0,
+                             None if ws is None else _p(ws), nbytes, _stream()), "vtx_seg_labels")
+    return labels
+
+
+def boundary_counts(pred, gt, n_obj, radius, out=None):
+    """counts int64 [N, n_obj, 4] = (|b_pred|, |b_gt|, |b_pred & dil(b_gt)|, |b_gt & dil(b_pred)|) per map and object
+    1..n_obj of int32 label maps ``pred`` / ``gt`` [N, H, W]; boundary and disk: include/vtx_vos.h."""
+    _dev(pred, gt)
+    if pred.dim() != 3 or pred.shape != gt.shape or pred.dtype != torch.int32 or gt.dtype != torch.int32:
+        raise VtxError("vtx: boundary_counts takes two int32 label maps of one [N, H, W] shape")
+    N, H, W = pred.shape
+    n_obj = int(n_obj)
+    counts = _into(out, (N, max(n_obj, 0), 4), torch.int64, pred.device, "counts")
+    lib = _lib.load()
+    nbytes = lib.vtx_boundary_workspace(N, n_obj, H, W)
+    ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=pred.device)
+    check(lib.vtx_boundary_counts(_p(pred), _p(gt), _p(counts), N, H, W, n_obj, int(radius), _p(ws), nbytes, _stream()),
+          "vtx_boundary_counts")
+    return counts
+
+
 # ------------------------------------------------------------------------------- attention maps (csrc/attention_maps.hip)
 def _attn_map_operands(q, k, n_head, what):
     """(B, Lq, Lk, D, ldq, ldkv) of a query view (B, Lq, >= nH D) and a key view (B, Lk, >= nH D) whose first nH * D columns are

@@ -15,10 +15,18 @@ Rules (include/vtx.h has them in full): neighbours are the first k candidates in
 index first" -- exactly k, where the composition keeps every key that ties with the k-th; weights and sums are fp32 in
 neighbour order.  Everywhere else the numbers are those of the composition.
 
-Out of scope here: resizing one-hot annotations down to the patch grid and soft labels up to the image (``F.interpolate``,
-the caller's), the boundary measure F, reading DAVIS, non-square position tables, and helpers for Swin / PVT / Twins (the
-functional entries take the tokens of any h x w grid).
+The evaluation that follows (csrc/davis.hip, include/vtx_vos.h) stays on the device too: ``labels_from_soft`` turns soft
+labels into label maps (bilinear upsample by the patch size, DINO's per-channel min-max normalisation, argmax, nearest resize
+-- one kernel, the upsampled tensor never exists), ``boundary_counts`` / ``boundary_measure`` give the boundary measure F of
+davis2017-evaluation (boundary bit rows, a disk dilation in LDS, population counts), and ``davis_jf`` chains annotation ->
+propagation -> label maps -> J and F without a host synchronisation.
+
+Out of scope here: reading DAVIS, void pixels, PIL-exact nearest resizing (the integer pixel-centre rule is used: see
+include/vtx_vos.h), non-integer scale factors, non-square position tables, and helpers for Swin / PVT / Twins (the functional
+entries take the tokens of any h x w grid).
 """
+import math
+
 import torch
 
 from . import ops
@@ -222,3 +230,154 @@ def jaccard_of_counts(counts):
     c = counts.double()
     inter, union = c[..., 0], c[..., 1] + c[..., 2] - c[..., 0]
     return torch.where(union > 0, inter / union.clamp_min(1.0), torch.ones_like(union))
+
+
+# ------------------------------------------------------------------------------------------------ DAVIS J&F
+def _label_maps(pred, gt, what):
+    for t in (pred, gt):
+        if not torch.is_tensor(t) or t.dim() < 3 or t.is_floating_point() or t.dtype == torch.bool:
+            raise VtxError(f"vtx: {what} takes integer label maps [..., H, W]")
+        if not t.is_cuda:
+            raise VtxError(f"vtx: {what} needs device tensors (there is no CPU fallback)")
+    if pred.shape != gt.shape:
+        raise VtxError(f"vtx: {what}: maps of shapes {tuple(pred.shape)} and {tuple(gt.shape)}")
+
+
+def _nearest_index(n_out, n_in, device):
+    """Source index of every output index under the integer pixel-centre rule ((2 i + 1) n_in) div (2 n_out)."""
+    i = torch.arange(n_out, dtype=torch.int64, device=device)
+    return ((2 * i + 1) * n_in) // (2 * n_out)
+
+
+def labels_from_soft(seg, scale, out_size=None, normalize=True):
+    """int32 label maps [N, oh, ow] (or [B, T, oh, ow]) of soft labels ``seg`` fp32 [N, C, gh, gw] (or [B, T, C, gh, gw],
+    propagate_video's output): bilinear upsample by the integer ``scale`` (1..32; the patch size), with ``normalize`` DINO's
+    per-channel (x - min) / (max - min) over the upsampled map where max > 0, argmax over C (at most 256 channels; the
+    lower channel wins ties), nearest resize to ``out_size`` = (oh, ow) (None: the upsampled size) by the integer
+    pixel-centre rule.  One kernel over the output pixels plus one for the extrema; rules: include/vtx_vos.h."""
+    if not torch.is_tensor(seg) or seg.dim() not in (4, 5) or seg.dtype != torch.float32:
+        raise VtxError("vtx: labels_from_soft takes float32 soft labels [N, C, gh, gw] or [B, T, C, gh, gw]")
+    if not seg.is_cuda:
+        raise VtxError("vtx: labels_from_soft needs device tensors (there is no CPU fallback)")
+    if not 1 <= int(scale) <= 32:
+        raise VtxError(f"vtx: labels_from_soft upsamples by an integer factor in 1..32, got {scale}")
+    lead, (C, gh, gw) = tuple(seg.shape[:-3]), seg.shape[-3:]
+    if not 1 <= C <= 256 or seg.numel() == 0:
+        raise VtxError(f"vtx: labels_from_soft takes 1 to 256 channels on a non-empty grid, got {tuple(seg.shape)}")
+    oh = ow = 0
+    if out_size is not None:
+        try:
+            oh, ow = (int(v) for v in out_size)
+        except (TypeError, ValueError):
+            raise VtxError("vtx: out_size is (oh, ow)") from None
+        if oh < 1 or ow < 1:
+            raise VtxError(f"vtx: out_size must be positive, got {(oh, ow)}")
+    out = ops.seg_labels(seg.detach().reshape((-1, C, gh, gw)).contiguous(), int(scale), oh, ow, bool(normalize))
+    return out.reshape(lead + tuple(out.shape[1:]))
+
+
+def boundary_radius(H, W, bound_pix=None, bound_th=0.008):
+    """The dilation radius of davis2017-evaluation's f_measure: ``bound_pix`` if given, else ``bound_th`` if it is >= 1, else
+    ceil(bound_th sqrt(H^2 + W^2)) in double on the host (8 at 480 x 854)."""
+    if bound_pix is None:
+        bound_pix = bound_th if bound_th >= 1 else math.ceil(bound_th * math.sqrt(float(H) * H + float(W) * W))
+    r = int(bound_pix)
+    if not 0 <= r <= 32:
+        raise VtxError(f"vtx: the boundary tolerance must be 0 to 32 pixels, got {bound_pix}")
+    return r
+
+
+def boundary_counts(pred, gt, n_obj, bound_pix=None, bound_th=0.008):
+    """int64 [..., n_obj, 4] = (|b_pred|, |b_gt|, |b_pred & dil(b_gt)|, |b_gt & dil(b_pred)|) per map and object 1..n_obj of
+    integer label maps ``pred`` / ``gt`` [..., H, W]: seg2bmap's boundary of every object mask, dilated by the disk of
+    ``boundary_radius(H, W, bound_pix, bound_th)`` pixels with zeros outside the map."""
+    _label_maps(pred, gt, "boundary_counts")
+    if not 1 <= int(n_obj) <= 255:
+        raise VtxError(f"vtx: boundary_counts counts 1 to 255 objects, got {n_obj}")
+    H, W = pred.shape[-2:]
+    radius = boundary_radius(H, W, bound_pix, bound_th)
+    counts = ops.boundary_counts(pred.reshape(-1, H, W).to(torch.int32).contiguous(), gt.reshape(-1, H, W).to(torch.int32).contiguous(),
+                                 int(n_obj), radius)
+    return counts.reshape(tuple(pred.shape[:-2]) + (int(n_obj), 4))
+
+
+def f_of_counts(counts):
+    """float64 [...] boundary measure F = 2 P R / (P + R) (0 where P + R = 0) of integer counts [..., 4] = (|b_pred|, |b_gt|,
+    match_pred, match_gt): P = match_pred / |b_pred|, R = match_gt / |b_gt|, with davis2017-evaluation's corner cases --
+    |b_pred| = 0 < |b_gt|: P = 1, R = 0; |b_gt| = 0 < |b_pred|: P = 0, R = 1; both empty: P = R = 1.  Runs where ``counts``
+    lives."""
+    c = counts.double()
+    nbp, nbg, mp, mg = c[..., 0], c[..., 1], c[..., 2], c[..., 3]
+    one, zero = torch.ones_like(nbp), torch.zeros_like(nbp)
+    P = torch.where(nbp > 0, torch.where(nbg > 0, mp / nbp.clamp_min(1.0), zero), one)
+    R = torch.where(nbg > 0, torch.where(nbp > 0, mg / nbg.clamp_min(1.0), zero), one)
+    s = P + R
+    return torch.where(s > 0, 2.0 * P * R / torch.where(s > 0, s, one), zero)
+
+
+def boundary_measure(pred, gt, n_obj, bound_pix=None, bound_th=0.008):
+    """The boundary measure F per map and object, float64 [..., n_obj]: ``f_of_counts(boundary_counts(...))``; next to
+    ``region_similarity``."""
+    return f_of_counts(boundary_counts(pred, gt, n_obj, bound_pix, bound_th))
+
+
+def first_frame_labels(label_map, patch, n_obj=None, grid=None):
+    """One-hot fp32 [B, n_obj + 1, gh, gw] of the first frame's annotation ``label_map`` [B, H, W] (integers, 0 = background)
+    on the patch grid -- the ``first_seg`` propagate_video wants.  Grid point (i, j) takes the label at the integer
+    pixel-centre rule of labels_from_soft, (((2 i + 1) H) div (2 gh), ((2 j + 1) W) div (2 gw)); with the default
+    ``grid`` = (H // patch, W // patch) and H, W multiples of ``patch`` that is ``label_map[:, patch // 2::patch,
+    patch // 2::patch]``.  A label outside 0..n_obj gives an all-zero point.  Plain indexing and one scatter, no kernel.
+    ``n_obj`` = None takes the largest label of the map (one host synchronisation)."""
+    if not torch.is_tensor(label_map) or label_map.dim() != 3 or label_map.is_floating_point() or label_map.dtype == torch.bool:
+        raise VtxError("vtx: first_frame_labels takes an integer label map [B, H, W]")
+    if not label_map.is_cuda:
+        raise VtxError("vtx: first_frame_labels needs device tensors (there is no CPU fallback)")
+    B, H, W = label_map.shape
+    if int(patch) < 1:
+        raise VtxError(f"vtx: the patch size must be positive, got {patch}")
+    try:
+        gh, gw = (H // int(patch), W // int(patch)) if grid is None else (int(g) for g in grid)
+    except (TypeError, ValueError):
+        raise VtxError("vtx: grid is (gh, gw)") from None
+    if gh < 1 or gw < 1 or B < 1:
+        raise VtxError(f"vtx: a {H} x {W} map gives no {gh} x {gw} grid")
+    if n_obj is None:
+        n_obj = max(int(label_map.max()), 0)
+    if not 0 <= int(n_obj) <= 255:
+        raise VtxError(f"vtx: first_frame_labels takes 0 to 255 objects, got {n_obj}")
+    lab = label_map[:, _nearest_index(gh, H, label_map.device)][:, :, _nearest_index(gw, W, label_map.device)].long()
+    idx = lab.clamp(0, int(n_obj)).unsqueeze(1)
+    out = torch.zeros((B, int(n_obj) + 1, gh, gw), dtype=torch.float32, device=label_map.device)
+    return out.scatter_(1, idx, (idx == lab.unsqueeze(1)).float())
+
+
+def davis_jf(model, frames, label_maps, n_obj, patch, bound_pix=None, bound_th=0.008, **propagate_kwargs):
+    """The DAVIS-2017 semi-supervised evaluation of a batch of videos: ``frames`` [B, T, 3, H, W], ``label_maps`` integer
+    [B, T, H0, W0] (frame 0's is the given annotation, the others the ground truth), objects 1..``n_obj``, ``patch`` the
+    model's patch size.  first_frame_labels -> propagate_video(**propagate_kwargs) -> labels_from_soft(out_size = (H0, W0))
+    -> region_similarity and boundary_measure on frames 1 .. T - 2 (DAVIS leaves out the first and the last frame).
+    -> dict of float64 device tensors: J, F [B, T - 2, n_obj], J_mean, F_mean, JF_mean (scalars; means over videos, frames
+    and objects), and the int32 label maps ``labels`` [B, T, H0, W0].  Nothing synchronises with the host."""
+    if not torch.is_tensor(frames) or frames.dim() != 5 or not torch.is_tensor(label_maps) or label_maps.dim() != 4 \
+            or label_maps.is_floating_point() or label_maps.dtype == torch.bool:
+        raise VtxError("vtx: davis_jf takes frames [B, T, 3, H, W] and integer label maps [B, T, H0, W0]")
+    if not frames.is_cuda or not label_maps.is_cuda:
+        raise VtxError("vtx: davis_jf needs device tensors (there is no CPU fallback)")
+    B, T = frames.shape[:2]
+    if tuple(label_maps.shape[:2]) != (B, T):
+        raise VtxError(f"vtx: davis_jf: frames {tuple(frames.shape)} and label maps {tuple(label_maps.shape)} are not one batch of videos")
+    if T < 3:
+        raise VtxError(f"vtx: davis_jf scores frames 1 .. T - 2 and needs T >= 3, got {T}")
+    if not 1 <= int(n_obj) <= 255 or not 1 <= int(patch) <= 32:
+        raise VtxError(f"vtx: davis_jf takes 1 to 255 objects and a patch size in 1..32, got {n_obj} and {patch}")
+    n_obj, patch = int(n_obj), int(patch)
+    grid = (frames.shape[3] // patch, frames.shape[4] // patch)
+    first = first_frame_labels(label_maps[:, 0], patch, n_obj, grid)
+    soft = propagate_video(model, frames, first, **propagate_kwargs)
+    labels = labels_from_soft(soft, patch, out_size=tuple(label_maps.shape[-2:]))
+    pred = labels[:, 1:T - 1].reshape((B * (T - 2),) + tuple(labels.shape[-2:]))
+    gt = label_maps[:, 1:T - 1].reshape(pred.shape)
+    J = region_similarity(pred, gt, n_obj).reshape(B, T - 2, n_obj)
+    F = boundary_measure(pred, gt, n_obj, bound_pix, bound_th).reshape(B, T - 2, n_obj)
+    J_mean, F_mean = J.mean(), F.mean()
+    return dict(J=J, F=F, J_mean=J_mean, F_mean=F_mean, JF_mean=(J_mean + F_mean) / 2, labels=labels)
